@@ -15,7 +15,13 @@ same 2048 kernels split over the N GPUs), and configs[3]: Zipf record streams at
 simulated ranks (47,482 {slot, ns} records per rank, kernel k pushed floor(8192/k^1.1)
 times, 1.3x stragglers) -> bucket by slot -> length-classed stats -> scores.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps of the value workload and prints the line with
+the headline figure (value, ms_per_step).  --full adds everything else to the line: the same loop
+with the default host wait, the statistics kernel's roofline, the one-report-at-a-time launch
+mode, the secondary legs, the CPU baselines and the drop-in API (--no-* switches apply there).
+--dump-outputs DIR writes the results of the last timed step (scores, straggler masks, error
+word) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 N > 1: one process per GPU over RCCL.  Under torchrun (WORLD_SIZE set) every process is one
 rank; run directly with --gpus N > 1, this script starts `torch.distributed.run
 --nproc-per-node N` on itself as a CHILD process (before anything touches the GPU) and exits
@@ -224,11 +230,15 @@ def phases_label(rep, g) -> str:
 
 
 def run_config(cfg, K_global, steps, warmup, world, rank, dev, time_kernel=True, use_graph=True,
-               graph_phases=False):
+               graph_phases=False, lean=False):
     """Full reports on one configuration.  use_graph: every report replays HIP graphs of the
     same kernels (one graph launch instead of one host launch per operation) -- on 1 GPU two
     whole-report graphs in flight (MatrixReporter.pipelined), on N GPUs the stats graph, the
-    eager partials exchange, then the rest; the stats phase is timed with HIP events."""
+    eager partials exchange, then the rest; the stats phase is timed with HIP events.
+    lean: the warm-up and the timed loop only (no bounded-wait loop, no statistics-kernel
+    timing, no graph phases).  "res_last" is the result of the timed loop's last report."""
+    if lean:
+        time_kernel = graph_phases = False
     R, s_push, cap = cfg["R"], cfg["s_push"], cfg["cap"]
     ns, kidx = make_shard(R, K_global, s_push, world, rank, dev)
     K_local = len(kidx)
@@ -244,7 +254,21 @@ def run_config(cfg, K_global, steps, warmup, world, rank, dev, time_kernel=True,
         ns_alt, _ = make_shard(R, K_global, s_push, world, rank, dev, seed=SEED_ALT)
         pipe = rep.pipelined([ns, ns_alt], s_push, timing=time_kernel, timing_reps=TIMED_REPS)
         warm_pipelined(pipe, warmup, world)
+        # the warm-up's report count depends on the clock (WARMUP_MIN_MS): one more untimed
+        # report where needed, so that the timed loop starts on the first input set on every run
+        # and its last report reads the same input whenever the arguments are the same
+        while pipe.n % pipe.depth:
+            pipe.submit()
+            pipe.collect()
         res, elapsed = timed_pipe_loop(pipe, steps, world, "spin")
+        res_last = res
+        keep = min(s_push, cap)
+        if lean:
+            label = pipe_label(pipe)
+            del ns_alt, pipe
+            return dict(ns=ns, kidx=kidx, rep=rep, res=res, res_last=res_last, elapsed=elapsed,
+                        kern_ms=None, samples=R * K_local * keep, nseg=R * K_local, keep=keep,
+                        launch=label, phases=None)
         # the same loop with the API's default host wait (bounded spin, then block)
         res_b, elapsed_bounded = timed_pipe_loop(pipe, steps, world, "bounded")
         # the roofline's kernel time: after the throughput loop, same process and buffers,
@@ -261,7 +285,6 @@ def run_config(cfg, K_global, steps, warmup, world, rank, dev, time_kernel=True,
             batch.set_sync_mode(prev)
             barrier(world)
         res = on_first_input(pipe)
-        keep = min(s_push, cap)
         phases = None
         if graph_phases:
             # one report at a time (statistics graph between timing events, then the rest; N
@@ -278,7 +301,7 @@ def run_config(cfg, K_global, steps, warmup, world, rank, dev, time_kernel=True,
                           launch=phases_label(rep, g), sets=res_p.stragglers_relative)
         label = pipe_label(pipe)
         del ns_alt, pipe
-        return dict(ns=ns, kidx=kidx, rep=rep, res=res, elapsed=elapsed,
+        return dict(ns=ns, kidx=kidx, rep=rep, res=res, res_last=res_last, elapsed=elapsed,
                     elapsed_bounded=elapsed_bounded,
                     sets_bounded_ok=bool(np.array_equal(res_b.stragglers_relative, res.stragglers_relative)),
                     kern_ms=float(np.mean(ks)) if ks else None,
@@ -288,10 +311,10 @@ def run_config(cfg, K_global, steps, warmup, world, rank, dev, time_kernel=True,
     res, elapsed, kern_ms = phases_loop(rep, ns, s_push, None, steps, world, time_kernel)
     keep = min(s_push, cap)
     launch = phases_label(rep, None)
-    return dict(ns=ns, kidx=kidx, rep=rep, res=res, elapsed=elapsed, kern_ms=kern_ms,
+    return dict(ns=ns, kidx=kidx, rep=rep, res=res, res_last=res, elapsed=elapsed, kern_ms=kern_ms,
                 samples=R * K_local * keep, nseg=R * K_local, keep=keep, launch=launch,
-                phases=dict(elapsed=elapsed, kern_ms=kern_ms, launch=launch,
-                            sets=res.stragglers_relative))
+                phases=None if lean else dict(elapsed=elapsed, kern_ms=kern_ms, launch=launch,
+                                              sets=res.stragglers_relative))
 
 
 def score_digest(res) -> dict:
@@ -299,6 +322,20 @@ def score_digest(res) -> dict:
     digest on N ranks equals the single-GPU one up to the f64 rounding of the shard combine."""
     return dict(rel_sum=float(np.nansum(res.gpu_relative)), ind_sum=float(np.nansum(res.gpu_individual)),
                 stragglers_rel=[int(i) for i in np.nonzero(res.stragglers_relative)[0]])
+
+
+def dump_outputs(path: str, res) -> None:
+    """--dump-outputs: a report's results as a caller receives them (batch.BatchResult), one
+    <field>.npy each -- the f64 scores as they are, the straggler masks and the error word as
+    float32."""
+    os.makedirs(path, exist_ok=True)
+    for name, a, dt in (("gpu_relative", res.gpu_relative, np.float64),
+                        ("gpu_individual", res.gpu_individual, np.float64),
+                        ("stragglers_relative", res.stragglers_relative, np.float32),
+                        ("stragglers_individual", res.stragglers_individual, np.float32),
+                        ("err", [res.err], np.float32)):
+        if a is not None:
+            np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=dt))
 
 
 def gather_labels(label: str, world: int):
@@ -545,6 +582,12 @@ def main():
     ap.add_argument("--zipf-cpu-ranks", type=int, default=1024)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP graph replay")
     ap.add_argument("--dry-run", action="store_true", help="launcher + rendezvous only (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: bounded-wait loop, roofline, "
+                         "graph phases, the 4096-rank and Zipf legs, CPU baselines, drop-in API")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results (what a caller of the report "
+                         "receives) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -565,16 +608,14 @@ def main():
     # ---------------- value: configs[1] per GPU, kernel-hash sharded (weak) ----------
     K_global = C2["K"] * world
     r = run_config(C2, K_global, args.steps, args.warmup, world, rank, dev, use_graph=not args.no_graph,
-                   graph_phases=not args.no_graph)
+                   graph_phases=not args.no_graph, lean=not args.full)
+    if args.dump_outputs and rank == 0:  # (after the combine every rank holds the same results)
+        dump_outputs(args.dump_outputs, r["res_last"])
     tmax = allreduce(r["elapsed"], torch.distributed.ReduceOp.MAX if world > 1 else None, world, dev)
     total_samples = allreduce(float(r["samples"]), torch.distributed.ReduceOp.SUM if world > 1 else None,
                               world, dev)
     value = total_samples * args.steps / tmax
     ms_per_step = tmax / args.steps * 1e3
-    # roofline of the dominant kernel (segment stats) on this GPU
-    alg_bytes = 4 * r["samples"] + STATS_BYTES_PER_SEGMENT * r["nseg"]
-    kern_ms = comm_max(r["kern_ms"], world, dev)  # the slowest rank's stats kernel
-    achieved = alg_bytes / (kern_ms * 1e-3)
     res = r["res"]
     strag_true = synth.straggler_ranks(C2["R"])
     sets_ok = all_ranks(bool(np.array_equal(res.stragglers_relative, strag_true.astype(bool))),
@@ -582,8 +623,47 @@ def main():
     # what the process group itself reports (not the launcher's --gpus)
     world_reported = (torch.distributed.get_world_size()
                       if torch.distributed.is_available() and torch.distributed.is_initialized() else 1)
-    sec_steps = max(10, args.steps // 2)  # the configs[2] / configs[3] legs
     launch_per_rank = gather_labels(r["launch"], world)
+    line = {
+        "metric": "duration samples/s reduced to perf scores; report latency at 4096 ranks",
+        "value": value,
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup, "warmup_min_ms": WARMUP_MIN_MS,
+        "ms_per_step": ms_per_step,
+        # the timed loop's host waits poll (batch.set_sync_mode("spin"))
+        "host_wait": "spin", "inputs_in_flight": INPUTS_IN_FLIGHT,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic",
+        "config": {"workload": "configs[1]: 64 simulated ranks x 2048 kernels/GPU x 10000 "
+                               "int-ns samples pushed (last 8192 kept), full stats + rel/indiv "
+                               "scores + straggler sets (thr 0.8)",
+                   "ranks": C2["R"], "kernels_per_gpu": C2["K"], "kernels_total": K_global,
+                   "samples_pushed": C2["s_push"], "ring_cap": C2["cap"],
+                   "parallelism": f"kernel-hash shards x{world}" if world > 1 else "1 GPU",
+                   "world_size": world, "world_size_reported": world_reported,
+                   "kernels_per_rank": shard_sizes(K_global, world),
+                   "backend": backend or "none (1 GPU)",
+                   "stats_mode": "fast", "launch": r["launch"], "launch_per_rank": launch_per_rank,
+                   "inputs_in_flight": INPUTS_IN_FLIGHT},
+        "straggler_sets_exact": sets_ok,
+    }
+    if not args.full:
+        # a plain run: the headline figure only (everything below takes runs of its own)
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    # roofline of the dominant kernel (segment stats) on this GPU
+    alg_bytes = 4 * r["samples"] + STATS_BYTES_PER_SEGMENT * r["nseg"]
+    kern_ms = comm_max(r["kern_ms"], world, dev)  # the slowest rank's stats kernel
+    achieved = alg_bytes / (kern_ms * 1e-3)
+    sec_steps = max(10, args.steps // 2)  # the configs[2] / configs[3] legs
     # the same workload one report at a time (graph phases), measured after the timed loop
     ph = r["phases"]
     phases = None
@@ -707,39 +787,15 @@ def main():
         # the committed PMC pass is of the 1-GPU launch (64 x 2048 segments); a shard of
         # 2048*N hashed kernels has a different size, so its traffic is not claimed
         traffic = pmc_traffic("c2_segment_stats") if world == 1 else None
-        line = {
-            "metric": "duration samples/s reduced to perf scores; report latency at 4096 ranks",
-            "value": value,
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup, "warmup_min_ms": WARMUP_MIN_MS,
-            "ms_per_step": ms_per_step,
+        line.update({
             # the one-report-at-a-time launch mode's time per report on the same workload,
             # measured after the pipelined loop on every N (a like-for-like 1 -> N
             # curve reads this field; "graph_phases" holds its label and rate)
             "ms_per_step_graph_phases": phases["ms_per_step"] if phases else None,
-            # the timed loop's host waits poll (batch.set_sync_mode("spin")); the batch API's
-            # default waits poll at most 50 us, then block -- the same loop in that mode:
-            "host_wait": "spin", "inputs_in_flight": INPUTS_IN_FLIGHT,
+            # the batch API's default host waits poll at most 50 us, then block -- the timed
+            # loop in that mode:
             "ms_per_step_bounded_wait": ms_bounded,
             "graph_phases": phases,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic",
-            "config": {"workload": "configs[1]: 64 simulated ranks x 2048 kernels/GPU x 10000 "
-                                   "int-ns samples pushed (last 8192 kept), full stats + rel/indiv "
-                                   "scores + straggler sets (thr 0.8)",
-                       "ranks": C2["R"], "kernels_per_gpu": C2["K"], "kernels_total": K_global,
-                       "samples_pushed": C2["s_push"], "ring_cap": C2["cap"],
-                       "parallelism": f"kernel-hash shards x{world}" if world > 1 else "1 GPU",
-                       "world_size": world, "world_size_reported": world_reported,
-                       "kernels_per_rank": shard_sizes(K_global, world),
-                       "backend": backend or "none (1 GPU)",
-                       "stats_mode": "fast", "launch": r["launch"], "launch_per_rank": launch_per_rank,
-                       "inputs_in_flight": INPUTS_IN_FLIGHT},
             "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK,
                          "traffic": traffic,
@@ -760,9 +816,8 @@ def main():
             "configs0_report": c1,
             "dropin_report_2048_kernels": api,
             "zipf_16384_ranks": zipf,
-            "straggler_sets_exact": sets_ok,
             "straggler_sets_exact_bounded_wait": sets_bounded,
-        }
+        })
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

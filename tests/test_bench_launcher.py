@@ -35,14 +35,62 @@ def test_launcher_two_ranks_dry_run():
 @pytest.mark.gpu
 @pytest.mark.timeout(400)
 def test_launcher_two_ranks_gloo_rehearsal():
-    line = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-zipf", "--no-cpu-baseline"],
-                timeout=380)
+    line = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-zipf",
+                 "--no-cpu-baseline"], timeout=380)
     assert line["n_gpus"] == 2
     assert line["config"]["world_size"] == 2 and line["config"]["backend"] == "gloo"
     assert line["config"]["kernels_total"] == 4096
     assert line["straggler_sets_exact"] is True
     assert line["latency_4096_ranks"]["straggler_sets_exact"] is True
     assert 0 < line["roofline"]["frac"] < 1.5
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+
+    import bench
+    from nvidia_resiliency_ext.straggler import batch
+
+    res = batch.BatchResult(np.array([1.0, np.nan]), None, np.array([False, True]), None, err=3)
+    bench.dump_outputs(str(tmp_path / "d"), res)
+    got = {p.name: np.load(p) for p in (tmp_path / "d").iterdir()}
+    assert sorted(got) == ["err.npy", "gpu_relative.npy", "stragglers_relative.npy"]
+    assert got["gpu_relative.npy"].dtype == np.float64
+    assert np.array_equal(got["gpu_relative.npy"], res.gpu_relative, equal_nan=True)
+    assert got["stragglers_relative.npy"].dtype == np.float32
+    assert got["stragglers_relative.npy"].tolist() == [0.0, 1.0]
+    assert got["err.npy"].tolist() == [3.0]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(240)
+def test_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run prints the headline line only (what --full adds is absent), --steps sets the
+    timed steps, and two runs with the same arguments dump identical results: the last timed
+    report reads the same seeded input whatever the warm-up's clock-bound report count was."""
+    import numpy as np
+
+    dumps = []
+    for d in ("a", "b"):
+        line = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                     str(tmp_path / d)], timeout=110)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["n_gpus"] == 1
+        assert line["unit"] == "samples/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "u32" and line["straggler_sets_exact"] is True
+        samples = 64 * 2048 * 8192  # retained samples per report
+        assert abs(line["value"] - samples / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+        for k in ("roofline", "latency_4096_ranks", "zipf_16384_ranks", "cpu_baseline",
+                  "graph_phases", "ms_per_step_bounded_wait", "dropin_report_2048_kernels"):
+            assert k not in line, k
+        dumps.append({p.name: np.load(p) for p in (tmp_path / d).iterdir()})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["err.npy", "gpu_individual.npy", "gpu_relative.npy",
+                                      "stragglers_individual.npy", "stragglers_relative.npy"]
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and a[name].shape == b[name].shape
+        assert np.array_equal(a[name], b[name], equal_nan=True), name
+    assert a["gpu_relative.npy"].shape == (64,) and a["err.npy"].tolist() == [0.0]
+    assert np.nonzero(a["stragglers_relative.npy"])[0].size > 0
 
 
 def test_launcher_four_ranks_dry_run():
@@ -56,7 +104,8 @@ def test_launcher_four_ranks_gloo_rehearsal():
     # the N > 1 line as the driver's 8-GPU node will print it, rehearsed with
     # 4 ranks on the one GPU over gloo: the world size the process group reports, the kernel
     # shard of every rank, and exact straggler sets (on every rank) for all three legs
-    line = _run(["--gpus", "4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], timeout=580)
+    line = _run(["--gpus", "4", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
+                timeout=580)
     cfg = line["config"]
     assert line["n_gpus"] == 4 and cfg["world_size"] == 4 and cfg["world_size_reported"] == 4
     assert cfg["backend"] == "gloo" and cfg["kernels_total"] == 4 * 2048
@@ -82,7 +131,8 @@ def test_launcher_four_ranks_gloo_rehearsal():
     gp = line["graph_phases"]
     assert gp["launch_per_rank"] == [want] * 4 and gp["straggler_sets_exact"] is True
     assert line["ms_per_step_graph_phases"] > 0
-    one = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], timeout=580)
+    one = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
+               timeout=580)
     alt = "hip_graph: reports two in flight, each on its own stream"
     assert one["zipf_16384_ranks"]["launch_per_rank"] == [alt] and one["config"]["launch"] == alt
     # configs[2] (34 GB of samples per report): whole reports on one stream (PIPE_ALT_MAX_BYTES)

@@ -13,19 +13,19 @@ mkdir -p "$OUT"
 has() { [[ " $STEPS " == *" $1 "* ]]; }
 cd "$R"
 if has bench; then
-  timeout -k 10 400 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 400 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   tail -1 "$OUT/bench.json" | cut -c1-300
 fi
 cd /tmp && export TMPDIR=/tmp
 if has trace; then
   timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- \
-      python3 "$R/bench.py" > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err"
+      python3 "$R/bench.py" --full > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err"
   echo trace done
 fi
 if has c2; then  # configs[1]: the headline's statistics kernel
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 300 rocprofv3 --pmc $c --output-format csv -d "$OUT/c2_$c" -o p -- \
-        python3 "$R/bench.py" --steps 3 --warmup 1 --no-latency4096 --no-zipf --no-cpu-baseline \
+        python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-latency4096 --no-zipf --no-cpu-baseline \
         > "$OUT/c2_$c.log" 2>&1
   done
   echo c2 done
