@@ -37,29 +37,6 @@ __device__ __forceinline__ int64_t stream_base(const int64_t* rec_off, int64_t t
     return ((rec_off[t] + 3) & ~(int64_t)3) + t * stream_slack(nslots);
 }
 
-// Timing-only ablation builds (tools/build_variant.sh -DNVRX_RB_ABLATE=k; outputs are wrong):
-// 1 = stop after pass 1 + the scans, 2 = also skip the staged copy-out and the tiny statistics
-// after pass 2, 3 = skip only the tiny statistics, 4 = pass 1's loads without the LDS slot counts,
-// then stop, 5 = pass 1 alone (no scans), 6 = pass 1 + the scan's chunk totals, 7 = pass 1 + the
-// scans without their global stores.  0 (the library): the whole kernel.
-#ifndef NVRX_RB_ABLATE
-#define NVRX_RB_ABLATE 0
-#endif
-// Timing-only probes of an in-place reduction of the hot slots (outputs are
-// wrong): NVRX_RB_HOTPASS = k adds k passes over the register head and the LDS stash after the
-// scan, each record of local slot < 32 adding one non-returning LDS atomic into a 32 x 256-bin
-// histogram (a radix-select level); NVRX_RB_HOTP1 = 1 adds ds_min / ds_max per hot record to
-// pass 1 (the slot's MIN / MAX).  Both use the cold-bucket stage as scratch.
-#ifndef NVRX_RB_TINY_COPY  // build-time switch: 1 = also write the reduced tiny buckets (and offsets) out
-#define NVRX_RB_TINY_COPY 0
-#endif
-#ifndef NVRX_RB_HOTPASS
-#define NVRX_RB_HOTPASS 0
-#endif
-#ifndef NVRX_RB_HOTP1
-#define NVRX_RB_HOTP1 0
-#endif
-
 constexpr uint32_t RB_OVF = 0x80000000u;  // start[s] flag: slot s overflowed its ring
 // Slots one bucketing pass counts in LDS; a larger slot table is bucketed in passes over
 // consecutive slot ranges (each pass re-reads the streams and ignores other slots' records),
@@ -70,10 +47,7 @@ constexpr int RB_TINY = 8;  // records_stats: buckets this short are reduced by 
 // records [lo, hi) of a stream in 16-byte pairs where the base allows it; f(rec) per record.
 // RB_UNROLL independent loads per lane are issued before any is consumed: a wave keeps
 // RB_UNROLL KB in flight instead of one (the loop is otherwise latency-bound).
-#ifndef NVRX_RB_UNROLL  // build-time tuning constant
-#define NVRX_RB_UNROLL 8
-#endif
-constexpr int RB_UNROLL = NVRX_RB_UNROLL;
+constexpr int RB_UNROLL = 8;
 template <class F>
 __device__ __forceinline__ void for_records(const nvrx_record* rs, int64_t lo, int64_t hi, int lane,
                                             bool pairs, F&& f) {
@@ -187,17 +161,9 @@ void records_bucket_kernel(
     }
     if (threadIdx.x == 0) any_ovf = force_stable ? 1u : 0u;
     __syncthreads();
-    uint32_t sink = 0;  // NVRX_RB_ABLATE == 4: the records consumed without the LDS counts
     const auto count = [&](const nvrx_record& r) {
         const uint32_t ls = r.slot - slot_lo;  // this pass's slots: [slot_lo, slot_lo + nslots)
-        if (NVRX_RB_ABLATE == 4)
-            sink += ls;
-        else if (ls < (uint32_t)nslots)
-            atomicAdd(&cnt[ls], 1u);
-        if (NVRX_RB_HOTP1 && ls < 32u && stage_cap >= 8192) {
-            atomicMin(&stage[2 * ls], r.ns);
-            atomicMax(&stage[2 * ls + 1], r.ns);
-        }
+        if (ls < (uint32_t)nslots) atomicAdd(&cnt[ls], 1u);
     };
     if (RB_REGS > 0) {  // issued first: their latency overlaps the LDS-stashed head
 #pragma unroll
@@ -220,10 +186,6 @@ void records_bucket_kernel(
     }
     for_records(rs, lo + 2 * (wpairs ? held : 0), hi, lane, wpairs, count);
     __syncthreads();
-    if (NVRX_RB_ABLATE == 5) {  // pass 1 alone (no scans)
-        if (threadIdx.x == 0 && cnt[0] == 0x12345u) counts[0] = 1;
-        return;
-    }
 
     // exclusive scan of padded keeps over slots, every wave on its own chunk of slots (the
     // block's other waves would otherwise wait at the barrier while one wave walks all the
@@ -265,10 +227,6 @@ void records_bucket_kernel(
         }
     }
     __syncthreads();
-    if (NVRX_RB_ABLATE == 6) {  // pass 1 + the scan's chunk totals only
-        if (threadIdx.x == 0 && wtot[0][0] == 0x12345u) counts[0] = 1;
-        return;
-    }
     uint32_t cold_total = 0, tiny_end = 0;
     {
         // the tier totals and this wave's carries from the waves' chunk totals: lane w reads
@@ -314,12 +272,10 @@ void records_bucket_kernel(
                     const int64_t g = t * seg_stride + slot_lo + s;
                     // a bucket this kernel reduces itself (after pass 2): a negative length
                     const bool reduced = tiny.num && k == 0 && keep >= 1 && st + padded <= lim;
-                    if (NVRX_RB_ABLATE != 7) {  // 7: the scans without their global stores
-                        // a reduced bucket's offset is never read (records_stats: not written)
-                        if (!reduced || NVRX_RB_TINY_COPY) seg_off[g] = ns_off + base + st;
-                        seg_len[g] = reduced ? -(int32_t)keep : (int32_t)keep;
-                        if (counts) counts[g] = (int32_t)total;  // optional in records_stats
-                    }
+                    // a reduced bucket's offset is never read (records_stats: not written)
+                    if (!reduced) seg_off[g] = ns_off + base + st;
+                    seg_len[g] = reduced ? -(int32_t)keep : (int32_t)keep;
+                    if (counts) counts[g] = (int32_t)total;  // optional in records_stats
                 }
                 carry0 += __builtin_amdgcn_readlane(i0, 63);
                 carry1 += __builtin_amdgcn_readlane(i1, 63);
@@ -329,11 +285,6 @@ void records_bucket_kernel(
         if (__ballot(overflow) != 0 && lane == 0) any_ovf = 1u;
     }
     __syncthreads();
-    if (NVRX_RB_ABLATE == 1 || NVRX_RB_ABLATE == 7) return;
-    if (NVRX_RB_ABLATE == 4) {
-        if (sink == 0x12345u) counts[0] = (int32_t)sink;  // keeps the loads alive
-        return;
-    }
     // positions below stage_lim go to LDS (cold buckets only: an overflowed slot's walk
     // writes to memory directly)
     const uint32_t stage_lim = (uint32_t)min((int64_t)cold_total, stage_cap);
@@ -363,26 +314,6 @@ void records_bucket_kernel(
             place(nvrx_record{w.z, w.w});
         }
     };
-    if (NVRX_RB_HOTPASS > 0 && stage_cap >= 8192) {
-        for (int lvl = 0; lvl < NVRX_RB_HOTPASS; ++lvl) {
-            const uint32_t sh = 24u - 8u * (uint32_t)lvl;
-            const auto hp = [&](uint32_t slot, uint32_t ns) {
-                const uint32_t ls = slot - slot_lo;
-                if (ls < 32u) atomicAdd(&stage[ls * 256u + ((ns >> sh) & 255u)], 1u);
-            };
-#pragma unroll
-            for (int u = 0; u < RB_REGS; ++u) {
-                hp(reg[u].x, reg[u].y);
-                hp(reg[u].z, reg[u].w);
-            }
-            for (int64_t k = lane; k < snp; k += 64) {
-                const u32x4 w = wstash[k];
-                hp(w.x, w.y);
-                hp(w.z, w.w);
-            }
-            __syncthreads();
-        }
-    }
     if (RB_REGS > 0) {  // no memory dependency: their atomics and stores go out first
 #pragma unroll
         for (int u = 0; u < RB_REGS; ++u) {
@@ -414,20 +345,19 @@ void records_bucket_kernel(
         // a chunk that is not pair-aligned (np = 0): its records one by one
         if (!wpairs) for_records(rs, lo, hi, lane, false, place);
     }
-    if (NVRX_RB_ABLATE == 2) return;
     if (stage_lim > 0) {  // the assembled head of the bucket array, in 16-byte stores
         __syncthreads();
         const u32x4* sv = (const u32x4*)stage;
         u32x4* ov = (u32x4*)out;  // out = stream base: 16-byte aligned
         // records_stats with the whole tiny tier staged: every tiny bucket is reduced below from
         // LDS and flagged (negative seg_len), so its records are never read from out_ns -- the
-        // copy-out starts past them (NVRX_RB_TINY_COPY=1 writes them anyway)
-        const uint32_t skip = (tiny.num && !NVRX_RB_TINY_COPY && tiny_end <= stage_lim) ? tiny_end / 4 : 0u;
+        // copy-out starts past them
+        const uint32_t skip = (tiny.num && tiny_end <= stage_lim) ? tiny_end / 4 : 0u;
         for (uint32_t i = skip + threadIdx.x; i < stage_lim / 4; i += blockDim.x) ov[i] = sv[i];
         // records_stats: the statistics of the staged buckets of <= RB_TINY records, one lane
         // per bucket straight from LDS (lane_stats: computeStats bit for bit, as the ragged
         // lane<8> class does), instead of a later kernel re-reading them through a class list
-        if (tiny.num && NVRX_RB_ABLATE != 3) {
+        if (tiny.num) {
             for (int64_t s = threadIdx.x; s < nslots; s += blockDim.x) {
                 const uint32_t total = cnt[s];
                 const uint32_t keep = keep_of(total);
@@ -487,37 +417,23 @@ int64_t records_bucket_capacity(int64_t n, int64_t nstreams, int64_t nslots) {
 }
 
 // dynamic LDS of a bucketing launch: a single workgroup may take the whole 160 KiB of a CU
-// (MI355X_MICROARCH.md), less the kernel's few static bytes.  NVRX_RB_LDS_KB (a build-time
-// tuning constant) caps it lower (round 4's variants that left class-kernel blocks room beside a
-// bucketing block: slower, profiles/r04/zipf_ab/).
-#ifndef NVRX_RB_LDS_KB
-#define NVRX_RB_LDS_KB 160
-#endif
-constexpr size_t RB_LAUNCH_LDS = (size_t)NVRX_RB_LDS_KB * 1024 - 256;
+// (MI355X_MICROARCH.md), less the kernel's few static bytes.  A lower RB_LDS_KB was slower
+// (round 4's variants that left class-kernel blocks room beside a bucketing block:
+// profiles/r04/zipf_ab/).
+constexpr int RB_LDS_KB = 160;
+constexpr size_t RB_LAUNCH_LDS = (size_t)RB_LDS_KB * 1024 - 256;
 // register-held record pairs per block, whatever the wave count: 16,384 pairs = 256 KiB =
 // 64 KiB per SIMD (half its register file) -- 4 waves x 64 pairs per lane (256 VGPRs),
 // 8 x 32 or 16 x 16 (64 VGPRs)
-#ifndef NVRX_RB_REGS_PER_BLOCK
-#define NVRX_RB_REGS_PER_BLOCK 16384
-#endif
-constexpr int RB_REGS_PER_BLOCK = NVRX_RB_REGS_PER_BLOCK;
-#ifndef NVRX_RB_STAGE_KB
-#define NVRX_RB_STAGE_KB 96
-#endif
-constexpr int RB_STAGE_KB = NVRX_RB_STAGE_KB;  // LDS staging of the cold buckets
-#ifndef NVRX_RB_COLD  // build-time tuning constant
-#define NVRX_RB_COLD 512
-#endif
-constexpr int RB_COLD = NVRX_RB_COLD;  // largest cold bucket (records)
+constexpr int RB_REGS_PER_BLOCK = 16384;
+constexpr int RB_STAGE_KB = 96;  // LDS staging of the cold buckets
+constexpr int RB_COLD = 512;     // largest cold bucket (records)
 
 // The shipped configuration: 16 waves x 16 register pairs per lane (4 waves / SIMD, 128
 // VGPRs), LDS stash interleaved with pass 2, 96 KiB of cold-bucket staging, cold = keep <= 512.
 // The alternatives measured on configs[3] (4 / 8 waves, no register pairs, 2-3 blocks per CU,
 // other stage sizes and cold limits, no stash) are in DESIGN.md section 3.4.
-#ifndef NVRX_RB_WAVES
-#define NVRX_RB_WAVES 16
-#endif
-constexpr int RB_WAVES = NVRX_RB_WAVES;
+constexpr int RB_WAVES = 16;
 constexpr int RB_REGS = RB_REGS_PER_BLOCK / (64 * RB_WAVES);
 
 static hipError_t records_bucket_pass(const nvrx_record* recs, const int64_t* rec_off, int64_t t0,

@@ -245,15 +245,13 @@ __device__ __forceinline__ void wide_moments(const uint32_t* p, int n, int64_t s
     }
 }
 
-#ifndef NVRX_BINS_PER_SAMPLE_SHORT  // build-time tuning constant: bins per lane-sample, PL <= 8
-#define NVRX_BINS_PER_SAMPLE_SHORT 16
-#endif
+constexpr int BINS_PER_SAMPLE_SHORT = 16;  // bins per lane-sample, PL <= 8
 template <int PL>
 struct Bins {
     // bins per wave: 16 per lane-sample for short segments (PL <= 16: C3's 1024 samples take
     // 256 bins -- fewer bucket-mates of the median to compact and rank, 3-5 % faster than 128,
     // while 512 was slower), 8 above (PL = 32 was fastest at 256)
-    static constexpr int PB = PL <= 8 ? NVRX_BINS_PER_SAMPLE_SHORT * PL : PL <= 16 ? 16 * PL : 8 * PL;
+    static constexpr int PB = PL <= 8 ? BINS_PER_SAMPLE_SHORT * PL : PL <= 16 ? 16 * PL : 8 * PL;
     static constexpr int NB = PB < 64 ? 64 : PB > 512 ? 512 : PB;
     static constexpr int BPL = NB / 64;                     // bins per lane
     static constexpr int LOG = (NB == 64) ? 6 : (NB == 128) ? 7 : (NB == 256) ? 8 : (NB == 512) ? 9 : 10;
@@ -322,9 +320,7 @@ struct OccV {  // the masked PL=128 variant gets the whole 256-register budget
 };
 
 // cache policy of the once-read sample stream (buffer-load aux bits)
-#ifndef NVRX_LOAD_AUX
-#define NVRX_LOAD_AUX 2  // nt: measured +1.5-2% on C2/C3 over the default policy
-#endif
+constexpr int LOAD_AUX = 2;  // nt: measured +1.5-2% on C2/C3 over the default policy
 
 // One wave per segment held in registers (v: 64*PL slots, lane-interleaved in 16-B vectors;
 // register i of lane L holds slot e = 256 (i >> 2) + 4 L + (i & 3) - m0).  MIN / MAX by wave
@@ -617,15 +613,6 @@ __device__ __forceinline__ LeanOut<PL> lean_core(unsigned (&v)[PL], int n, int m
     return LeanOut<PL>{mn, mx, d0 - B, d1 - B, c, sd, sq};
 }
 
-template <int PL>
-__device__ __forceinline__ unsigned lean_body(unsigned (&v)[PL], int n, unsigned x0, int64_t s,
-                                          unsigned* hist, const nvrx_stats_soa& out,
-                                          const ColRef& cr) {
-    const LeanOut<PL> r = lean_core<PL>(v, n, 0, x0, hist);
-    emit_stats(out, s, n, r.mn, r.mx, r.d0, r.d1, (double)r.sd, r.sq, r.c, cr);
-    return r.mx;
-}
-
 // HBM -> VGPR in two steps, so a caller can issue the next segment's loads before it
 // reduces the current one.  issue_loads: the segment p[0:n) into v (64*PL slots, see
 // lean_core) with 16-byte buffer loads from the 16-B aligned base below p; the descriptor
@@ -648,7 +635,7 @@ __device__ __forceinline__ void issue_loads(const uint32_t* p, int n, unsigned (
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(pbase, 0, nbytes, 0x00020000);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-        const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, j * 1024, NVRX_LOAD_AUX);
+        const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, j * 1024, LOAD_AUX);
         v[4 * j + 0] = q.x;
         v[4 * j + 1] = q.y;
         v[4 * j + 2] = q.z;
@@ -716,43 +703,21 @@ void seg_stats_fast_kernel(Segs segs, int64_t nseg, nvrx_stats_soa out, ColRef c
     if (r.mx >= NVRX_KEY_WIDE) wide_moments(p, n, s, out);
 }
 
-// FULL segments only (64*PL samples each, 16-B aligned): lean_body.
-template <int PL, class Segs>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Occ<PL>::W)))
-void seg_stats_lean_kernel(Segs segs, int64_t nseg, nvrx_stats_soa out, ColRef cr) {
-    constexpr int NB = Bins<PL>::NB;
-    __shared__ __attribute__((aligned(16))) unsigned lds_hist[4 * NB];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t s = (int64_t)blockIdx.x * 4 + wave;
-    if (s >= nseg) return;
-    unsigned* hist = lds_hist + wave * NB;
-    const uint32_t* p;
-    int n;
-    segs.get(s, p, n);
-    unsigned v[PL];
-    int m0;
-    unsigned x0;
-    load_segment<PL, true>(p, n, v, m0, x0);
-    if (lean_body<PL>(v, n, x0, s, hist, out, cr) >= NVRX_KEY_WIDE) wide_moments(p, n, s, out);
-}
-
 // FULL segments (configs[1] / configs[2]): each wave reduces `group` consecutive segments one
 // after another and keeps what lean_core returns for segment s0 + j in lane j (one compare and
 // nine selects), so the epilogue -- the unit conversions, the f64 quotients and the root, the
 // stores -- runs once per group, lane-parallel with coalesced stores, instead of once per
 // segment on one busy lane (~55 VALU, half of them f64).  Same arithmetic as emit_stats, so the
 // same bits.  Groups of up to 8 (lean_group): the sweep on configs[2] in DESIGN.md section 3.1.
-#ifndef NVRX_GROUP_WAVES  // waves per workgroup of the group kernel (build-time tuning constant)
-#define NVRX_GROUP_WAVES 4
-#endif
+constexpr int GROUP_WAVES = 4;  // waves per workgroup of the group kernel
 template <int PL, class Segs>
-__global__ __launch_bounds__(64 * NVRX_GROUP_WAVES) __attribute__((amdgpu_waves_per_eu(Occ<PL>::W)))
+__global__ __launch_bounds__(64 * GROUP_WAVES) __attribute__((amdgpu_waves_per_eu(Occ<PL>::W)))
 void seg_stats_lean_group_kernel(Segs segs, int64_t nseg, int group, nvrx_stats_soa out, ColRef cr) {
     constexpr int NB = Bins<PL>::NB;
-    __shared__ __attribute__((aligned(16))) unsigned lds_hist[NVRX_GROUP_WAVES * NB];
+    __shared__ __attribute__((aligned(16))) unsigned lds_hist[GROUP_WAVES * NB];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = lane_id();
-    const int64_t s0 = ((int64_t)blockIdx.x * NVRX_GROUP_WAVES + wave) * group;
+    const int64_t s0 = ((int64_t)blockIdx.x * GROUP_WAVES + wave) * group;
     if (s0 >= nseg) return;
     const int cnt = (int)(nseg - s0 < group ? nseg - s0 : group);
     unsigned* hist = lds_hist + wave * NB;
@@ -1144,45 +1109,32 @@ static inline hipError_t make_colref(uint32_t* col_ref, int64_t ncols, hipStream
     return hipGetLastError();
 }
 
-// segments per wave of the group kernel: up to NVRX_LEAN_GROUP_MAX while the grid keeps >= 32768 waves
-// Segments per wave of the group kernel: configs[2] statistics interleaved on one box
-// (tools/build_variant.sh + tools/gpu_r03_variants.sh, profiles/r03/group_size/): 4 / 6 / 8 / 12
-// / 32 / 64 per wave 5.70 / 5.87 / 5.57 / 5.78 / 6.04 / 5.87 ms (round-start library 6.00 ms);
-// a prefetch of the next segment's loads (80 VGPRs, 6 waves / SIMD) 5.90-5.94 at 64.  A build
-// constant, so A/B builds can override it.
-#ifndef NVRX_LEAN_GROUP_MAX
-#define NVRX_LEAN_GROUP_MAX 8
-#endif
+// Segments per wave of the group kernel: up to LEAN_GROUP_MAX while the grid keeps at least
+// LEAN_GROUP_WAVES waves.  configs[2] statistics interleaved on one box
+// (profiles/r03/group_size/): 4 / 6 / 8 / 12 / 32 / 64 per wave 5.70 / 5.87 / 5.57 / 5.78 / 6.04
+// / 5.87 ms (round-start library 6.00 ms); a prefetch of the next segment's loads (80 VGPRs,
+// 6 waves / SIMD) 5.90-5.94 at 64.
+constexpr int LEAN_GROUP_MAX = 8;
 // one segment's results per lane, wide-key flags in a 64-bit mask
-static_assert(NVRX_LEAN_GROUP_MAX >= 1 && NVRX_LEAN_GROUP_MAX <= 64, "NVRX_LEAN_GROUP_MAX in [1, 64]");
-#ifndef NVRX_LEAN_GROUP_PL_MAX  // FULL segments of up to 64 * this many samples take the group kernel
-#define NVRX_LEAN_GROUP_PL_MAX 128
-#endif
-#ifndef NVRX_LEAN_GROUP_WAVES  // build-time tuning constant: the fewest waves a grouped grid keeps
-#define NVRX_LEAN_GROUP_WAVES 32768
-#endif
+static_assert(LEAN_GROUP_MAX >= 1 && LEAN_GROUP_MAX <= 64, "LEAN_GROUP_MAX in [1, 64]");
+constexpr int LEAN_GROUP_WAVES = 32768;  // the fewest waves a grouped grid keeps
 static inline int lean_group(int64_t nseg) {
-    const int64_t g = nseg / NVRX_LEAN_GROUP_WAVES;
-    return g < 1 ? 1 : g > NVRX_LEAN_GROUP_MAX ? NVRX_LEAN_GROUP_MAX : (int)g;
+    const int64_t g = nseg / LEAN_GROUP_WAVES;
+    return g < 1 ? 1 : g > LEAN_GROUP_MAX ? LEAN_GROUP_MAX : (int)g;
 }
 
 template <int PL, class Segs>
 static void launch_pl(const Segs& segs, int64_t nseg, bool full, const nvrx_stats_soa& out,
                       const ColRef& cr, hipStream_t st) {
-    const dim3 grid((unsigned)((nseg + 3) / 4)), block(256);
-    // FULL: unmasked lean_core with the group epilogue (one segment per wave above
-    // NVRX_LEAN_GROUP_PL_MAX, a build-time choice); otherwise the masked lean_core
+    // FULL: unmasked lean_core with the group epilogue; otherwise the masked lean_core
     if (full) {
-        if constexpr (PL <= NVRX_LEAN_GROUP_PL_MAX) {
-            const int g = lean_group(nseg);
-            const int64_t waves = (nseg + g - 1) / g;
-            hipLaunchKernelGGL((seg_stats_lean_group_kernel<PL, Segs>),
-                               dim3((unsigned)((waves + NVRX_GROUP_WAVES - 1) / NVRX_GROUP_WAVES)),
-                               dim3(64 * NVRX_GROUP_WAVES), 0, st, segs, nseg, g, out, cr);
-        } else {
-            hipLaunchKernelGGL((seg_stats_lean_kernel<PL, Segs>), grid, block, 0, st, segs, nseg, out, cr);
-        }
+        const int g = lean_group(nseg);
+        const int64_t waves = (nseg + g - 1) / g;
+        hipLaunchKernelGGL((seg_stats_lean_group_kernel<PL, Segs>),
+                           dim3((unsigned)((waves + GROUP_WAVES - 1) / GROUP_WAVES)),
+                           dim3(64 * GROUP_WAVES), 0, st, segs, nseg, g, out, cr);
     } else {
+        const dim3 grid((unsigned)((nseg + 3) / 4)), block(256);
         hipLaunchKernelGGL((seg_stats_fast_kernel<PL, false, Segs>), grid, block, 0, st, segs, nseg, out, cr);
     }
 }

@@ -58,10 +58,7 @@ using namespace ragged;
 
 // The class kernels are dealt over the caller's stream and one side stream per device
 // (configs[3]: 4.28 -> 4.15 ms; 3 / 4 streams were no faster).
-#ifndef NVRX_RAGGED_STREAMS  // build-time tuning constant
-#define NVRX_RAGGED_STREAMS 2
-#endif
-constexpr int RAGGED_STREAMS = NVRX_RAGGED_STREAMS;
+constexpr int RAGGED_STREAMS = 2;
 struct Fork {
     hipStream_t s[RAGGED_STREAMS];  // s[0] unused: slot 0 is the caller's stream
     hipEvent_t fork, join[RAGGED_STREAMS];
@@ -143,66 +140,24 @@ hipError_t ragged_launch_classes(const RaggedSegs& segs, const uint32_t* cls_lis
         return i ? fk->s[i] : st;
     };
     const uint32_t* c = cls;
-    // the launches: (kind, size); kind 0 lane<size>, 1 list<size>, 2 FULL<size / 64>, 3 workgroup
-    struct L {
-        int kind, n;
-    };
-    L lane[5], wave[6], big[2];
-    int nl = 0, nw = 0, nb = 0;
-    for (int n = 8; n <= 128; n *= 2)
-        if (n == 8 || keep > n / 2) lane[nl++] = {0, n};
-    if (!exact) {
-        if (keep > 128) wave[nw++] = {1, 4};
-        for (int pl = 8; pl <= 128; pl *= 2)
-            if (need > 64 * (pl / 2)) wave[nw++] = {1, pl};
-        if (const int fn = full_len(keep, aligned16, exact)) big[nb++] = {2, fn};  // the FULL class
-    }
-    if (exact ? keep > 128 : need > 64 * 128) big[nb++] = {3, 0};
     // order: the long-segment classes first, then the wave classes, then the lane classes (a FULL
     // kernel last ran alone behind the others; DESIGN 3.2, profiles/r05/class_order_ab.log)
-#ifndef NVRX_CLASS_ORDER  // build-time tuning constant (timing A/B of the launch order)
-#define NVRX_CLASS_ORDER 2
-#endif
-    L order[13];
-    int no = 0;
-    const auto put = [&](const L* a, int n, bool rev) {
-        for (int i = 0; i < n; ++i) order[no++] = a[rev ? n - 1 - i : i];
-    };
-    switch (NVRX_CLASS_ORDER) {
-        case 0: put(lane, nl, false); put(wave, nw, false); put(big, nb, false); break;
-        case 1: put(big, nb, false); put(lane, nl, false); put(wave, nw, false); break;
-        case 2: put(big, nb, false); put(wave, nw, false); put(lane, nl, false); break;
-        case 3: put(big, nb, false); put(wave, nw, true); put(lane, nl, true); break;
-        case 4: put(big, nb, false); put(lane, nl, true); put(wave, nw, true); break;
-        case 6: put(big, nb, false); put(wave, nw, false); put(lane, nl, true); break;
-        default: {  // 5: big first, then wave and lane classes interleaved, longest first
-            put(big, nb, false);
-            for (int i = 0; i < std::max(nl, nw); ++i) {
-                if (i < nw) order[no++] = wave[nw - 1 - i];
-                if (i < nl) order[no++] = lane[nl - 1 - i];
-            }
-        }
-    }
     hipError_t e = hipSuccess;
-    for (int i = 0; i < no && e == hipSuccess; ++i) {
-        const L& o = order[i];
-        switch (o.kind) {
-            case 0: {
-                const int cl = o.n == 8 ? C_T8 : o.n == 16 ? C_T16 : o.n == 32 ? C_T32 : o.n == 64 ? C_T64 : C_T128;
-                ragged_launch_lane(o.n, segs, list, c + 2 * cl, aligned16, out, S());
-                break;
-            }
-            case 1: {
-                const int cl = o.n == 4 ? C_W4 : o.n == 8 ? C_W8 : o.n == 16 ? C_W16 : o.n == 32 ? C_W32
-                             : o.n == 64 ? C_W64 : C_W128;
-                ragged_launch_list(o.n, segs, list, c + 2 * cl, out, S());
-                break;
-            }
-            case 2: ragged_launch_full(o.n / 64, segs, list, c + 2 * C_F, out, S()); break;
-            default: e = ragged_launch_exact(segs, list, c + 2 * C_X, keep, out, S());
+    if (!exact)
+        if (const int fn = full_len(keep, aligned16, exact))  // the FULL class
+            ragged_launch_full(fn / 64, segs, list, c + 2 * C_F, out, S());
+    if (exact ? keep > 128 : need > 64 * 128)  // the workgroup class
+        e = ragged_launch_exact(segs, list, c + 2 * C_X, keep, out, S());
+    if (e == hipSuccess) {
+        if (!exact) {  // the wave classes, ascending PL: C_W4, C_W8 .. C_W128
+            if (keep > 128) ragged_launch_list(4, segs, list, c + 2 * C_W4, out, S());
+            for (int pl = 8, cl = C_W8; pl <= 128; pl *= 2, ++cl)
+                if (need > 64 * (pl / 2)) ragged_launch_list(pl, segs, list, c + 2 * cl, out, S());
         }
+        for (int n = 8, cl = C_T8; n <= 128; n *= 2, ++cl)  // the lane classes, ascending N
+            if (n == 8 || keep > n / 2) ragged_launch_lane(n, segs, list, c + 2 * cl, aligned16, out, S());
+        e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipGetLastError();
     // joined on every path: a side stream left forked would leave a graph capture unjoined
     if (fk) {
         const hipError_t j = ragged_join(st, fk);

@@ -20,10 +20,7 @@ constexpr int CLS_MAX_BLOCKS = 1024;
 // segment lengths loaded per thread before any is classified: a block's chunk is tens of
 // thousands of segments, and one dependent load per 1024 of them left both passes
 // latency-bound (configs[3]: 153 + 118 us for 33.5 M segments)
-#ifndef NVRX_CLS_BATCH  // build-time tuning constant
-#define NVRX_CLS_BATCH 8
-#endif
-constexpr int CLS_BATCH = NVRX_CLS_BATCH;
+constexpr int CLS_BATCH = 8;
 static_assert(CLS_BATCH >= 1 && CLS_BATCH < 16 && 4 * NCLASS <= 64, "4-bit packed class counts per batch");
 
 
@@ -218,22 +215,14 @@ template <int PL>
 struct ListGroup {  // one epilogue per chunk (emit_lane): the short classes, whose chunks are long
     static constexpr bool on = PL <= 8;
 };
-#ifndef NVRX_LIST4_OCC  // build-time tuning constants: waves per SIMD of list<4> / list<8>
-#define NVRX_LIST4_OCC 8
-#endif
-#ifndef NVRX_LIST8_OCC
-#define NVRX_LIST8_OCC 7
-#endif
+constexpr int LIST4_OCC = 8, LIST8_OCC = 7;  // waves per SIMD of list<4> / list<8>
 template <int PL>
 struct ListOcc {  // the prefetch buffer costs PL more VGPRs, the chunk's results nine
-    static constexpr int W = PL == 16 ? 6 : PL == 8 ? NVRX_LIST8_OCC : PL == 4 ? NVRX_LIST4_OCC : OccV<PL, false>::W;
+    static constexpr int W = PL == 16 ? 6 : PL == 8 ? LIST8_OCC : PL == 4 ? LIST4_OCC : OccV<PL, false>::W;
 };
-#ifndef NVRX_LIST_CHUNK  // build-time tuning constant (tools/build_variant.sh)
-#define NVRX_LIST_CHUNK 16
-#endif
-constexpr int LIST_CHUNK = NVRX_LIST_CHUNK;
+constexpr int LIST_CHUNK = 16;
 // results are held one per lane and the wide-key flags in a 32-bit mask
-static_assert(LIST_CHUNK >= 1 && LIST_CHUNK <= 32, "NVRX_LIST_CHUNK must be in [1, 32]");
+static_assert(LIST_CHUNK >= 1 && LIST_CHUNK <= 32, "LIST_CHUNK must be in [1, 32]");
 
 template <int PL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ListOcc<PL>::W)))
@@ -349,16 +338,14 @@ void seg_stats_list_kernel(RaggedSegs segs, const uint32_t* list, const uint32_t
 // configs[1] group kernel's body over a class list -- each wave takes LIST_FULL_GROUP consecutive
 // list entries, lanes 0..m-1 fetch their ids in one access, every segment runs the unmasked
 // lean_core, and segment j's results wait in lane j for one lane-parallel epilogue.
-#ifndef NVRX_LIST_FULL_GROUP  // build-time tuning constant
-#define NVRX_LIST_FULL_GROUP 4
-#endif
+constexpr uint32_t LIST_FULL_GROUP = 4;
 template <int PL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Occ<PL>::W)))
 void seg_stats_list_full_kernel(RaggedSegs segs, const uint32_t* list, const uint32_t* cls,
                                 nvrx_stats_soa out) {
     const ColRef cr{nullptr, nullptr, 1, 1.0};  // column references: kernel_ref afterwards
     constexpr int NB = Bins<PL>::NB;
-    constexpr uint32_t G = NVRX_LIST_FULL_GROUP;
+    constexpr uint32_t G = LIST_FULL_GROUP;
     __shared__ __attribute__((aligned(16))) unsigned lds_hist[4 * NB];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = lane_id();
