@@ -164,6 +164,29 @@ int nvrx_segment_stats_ragged(const uint32_t* ns, const int64_t* seg_off, const 
                               int32_t aligned16, const nvrx_stats_soa* out, uint32_t* col_ref,
                               int64_t ncols, void* stream);
 
+/* Tail quantiles of the same segments.  No reference counterpart (computeStats keeps MIN, MAX
+ * and MED only): the order statistics a straggler that is slow on every n-th call shows up in.
+ * A quantile is an integer permille pm in [0, 1000]; for a segment of n >= 1 retained samples
+ * (the last min(len, cap), as above) the result is the sample of 0-based rank
+ * (pm * (n - 1)) / 1000 (integer division, 64-bit) among the keys sorted ascending, converted to
+ * us like every other sample -- no interpolation, so pm = 0 / 1000 have MIN's / MAX's bits and
+ * pm = 500 of an odd n has MED's.  permille: HOST array of nq <= NVRX_MAX_QUANTILES entries
+ * (copied at the call; any order, repeats allowed); out: [nq][nseg] f32 us, quantile-major, in the
+ * order of permille; num: [nseg] retained lengths, or NULL.  An empty segment gives NaN and
+ * num 0; in the ragged call seg_len[s] < 0 skips segment s (outputs untouched).  Stream-ordered:
+ * kernels on `stream` only, no allocation, no synchronisation (capturable in a graph).
+ * Segments are read by their own retained length: up to 8192 samples in one wave's registers
+ * (one read of the segment), longer ones by a workgroup in four passes over memory. */
+#define NVRX_MAX_QUANTILES 8
+int nvrx_segment_quantiles_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
+                                   int64_t seg_begin, int64_t seg_len, int64_t cap,
+                                   const int32_t* permille, int32_t nq, float* out, int32_t* num,
+                                   void* stream);
+int nvrx_segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off,
+                                  const int32_t* seg_len, int64_t nseg, int64_t max_len,
+                                  int64_t cap, int32_t aligned16, const int32_t* permille,
+                                  int32_t nq, float* out, int32_t* num, void* stream);
+
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.
  * scratch: >= 2*K uint32 of device memory. */
@@ -299,6 +322,15 @@ int nvrx_profiler_get_stats(nvrx_profiler* p, int64_t cap_out, int64_t* count, u
                             int32_t* num, float* mn, float* mx, float* med, float* avg,
                             float* sd);
 int nvrx_profiler_kernel_name(nvrx_profiler* p, uint32_t slot, char* buf, int64_t buflen);
+/* Flush, then the quantiles (nvrx_segment_quantiles_ragged) of every slot with >= 1 record, over
+ * the records its ring retains.  Synchronous.  *count = number of kernels; fills up to cap_out
+ * entries of slots (sorted by kernel name, like get_stats), num (retained records) and out
+ * ([nq][cap_out] host f32 us: quantile j of entry i at out[j * cap_out + i]).  The record log and
+ * get_stats' cached result are left as they are; the call's own kernels are not captured.  No
+ * reference counterpart: CuptiProfiler::getStats has no quantile beyond the median. */
+int nvrx_profiler_get_quantiles(nvrx_profiler* p, const int32_t* permille, int32_t nq,
+                                int64_t cap_out, int64_t* count, uint32_t* slots, int32_t* num,
+                                float* out);
 /* Flush, then copy the record log since the last reset ({slot, ns}, push order per slot;
  * after a compaction only the records the rings can still retain) into host `out`
  * (up to cap_out records; *count = log length).  Synchronous.  No reference counterpart:

@@ -39,6 +39,18 @@ int hip_status(hipError_t e, const char* where) {
 
 hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// the quantile requests of nvrx_*_quantiles*: a host array of 1..NVRX_MAX_QUANTILES permilles
+int check_permille(const char* fn, const int32_t* permille, int32_t nq) {
+    if (nq < 1 || nq > NVRX_MAX_QUANTILES)
+        return fail(NVRX_ERR_INVALID, std::string(fn) + ": nq must be in [1, NVRX_MAX_QUANTILES = 8]");
+    if (!permille) return fail(NVRX_ERR_INVALID, std::string(fn) + ": null permille");
+    for (int32_t j = 0; j < nq; ++j)
+        if (permille[j] < 0 || permille[j] > 1000)
+            return fail(NVRX_ERR_INVALID, std::string(fn) + ": permille[" + std::to_string(j) +
+                                              "] outside [0, 1000]");
+    return NVRX_OK;
+}
+
 }  // namespace
 
 namespace nvrx {
@@ -119,6 +131,50 @@ int nvrx_segment_stats_ragged(const uint32_t* ns, const int64_t* seg_off, const 
     return hip_status(nvrx::segment_stats_ragged(ns, seg_off, seg_len, nseg, max_len, cap, mode,
                                                  aligned16 != 0, *out, col_ref, ncols, S(stream)),
                       "nvrx_segment_stats_ragged");
+}
+
+// ------------------------------------------------------------------ quantiles
+int nvrx_segment_quantiles_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
+                                   int64_t seg_begin, int64_t seg_len, int64_t cap,
+                                   const int32_t* permille, int32_t nq, float* out, int32_t* num,
+                                   void* stream) {
+    if (int rc = check_permille("nvrx_segment_quantiles_strided", permille, nq)) return rc;
+    NVRX_CHECK_ARG(nseg >= 0, "nvrx_segment_quantiles_strided: negative nseg");
+    NVRX_CHECK_ARG(seg_len >= 0, "nvrx_segment_quantiles_strided: negative seg_len");
+    NVRX_CHECK_ARG(seg_begin >= 0, "nvrx_segment_quantiles_strided: negative seg_begin");
+    NVRX_CHECK_ARG(seg_stride >= 0, "nvrx_segment_quantiles_strided: negative seg_stride");
+    NVRX_CHECK_ARG(nseg < (int64_t)1 << 31, "nvrx_segment_quantiles_strided: nseg must be below 2^31");
+    NVRX_CHECK_ARG(nseg == 0 || out, "nvrx_segment_quantiles_strided: null out");
+    NVRX_CHECK_ARG(nseg == 0 || seg_len == 0 || ns, "nvrx_segment_quantiles_strided: null ns");
+    NVRX_CHECK_ARG(nseg <= 1 || seg_stride >= seg_begin + seg_len,
+                   "nvrx_segment_quantiles_strided: segments overlap (seg_stride < seg_begin + seg_len)");
+    const int64_t keep = (cap > 0 && seg_len > cap) ? cap : seg_len;
+    NVRX_CHECK_ARG(keep <= NVRX_MAX_SEGMENT,
+                   "nvrx_segment_quantiles_strided: retained seg_len longer than NVRX_MAX_SEGMENT (2^30)");
+    if (nseg == 0) return NVRX_OK;
+    return hip_status(nvrx::segment_quantiles_strided(ns, nseg, seg_stride, seg_begin, seg_len, cap,
+                                                      permille, nq, out, num, S(stream)),
+                      "nvrx_segment_quantiles_strided");
+}
+
+int nvrx_segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off,
+                                  const int32_t* seg_len, int64_t nseg, int64_t max_len,
+                                  int64_t cap, int32_t aligned16, const int32_t* permille,
+                                  int32_t nq, float* out, int32_t* num, void* stream) {
+    if (int rc = check_permille("nvrx_segment_quantiles_ragged", permille, nq)) return rc;
+    NVRX_CHECK_ARG(nseg >= 0, "nvrx_segment_quantiles_ragged: negative nseg");
+    NVRX_CHECK_ARG(max_len >= 0, "nvrx_segment_quantiles_ragged: negative max_len");
+    NVRX_CHECK_ARG(nseg < (int64_t)1 << 31, "nvrx_segment_quantiles_ragged: nseg must be below 2^31");
+    NVRX_CHECK_ARG(nseg == 0 || out, "nvrx_segment_quantiles_ragged: null out");
+    NVRX_CHECK_ARG(nseg == 0 || seg_off, "nvrx_segment_quantiles_ragged: null seg_off");
+    NVRX_CHECK_ARG(nseg == 0 || max_len == 0 || ns, "nvrx_segment_quantiles_ragged: null ns");
+    const int64_t keep = (cap > 0 && max_len > cap) ? cap : max_len;
+    NVRX_CHECK_ARG(keep <= NVRX_MAX_SEGMENT,
+                   "nvrx_segment_quantiles_ragged: retained max_len longer than NVRX_MAX_SEGMENT (2^30)");
+    if (nseg == 0) return NVRX_OK;
+    return hip_status(nvrx::segment_quantiles_ragged(ns, seg_off, seg_len, nseg, max_len, cap,
+                                                     aligned16 != 0, permille, nq, out, num, S(stream)),
+                      "nvrx_segment_quantiles_ragged");
 }
 
 // ------------------------------------------------------------------ scoring
@@ -807,6 +863,61 @@ int nvrx_profiler_get_stats(nvrx_profiler* p, int64_t cap_out, int64_t* count, u
         if (med) med[i] = p->c_med[i];
         if (avg) avg[i] = p->c_avg[i];
         if (sd) sd[i] = p->c_sd[i];
+    }
+    return NVRX_OK;
+}
+
+int nvrx_profiler_get_quantiles(nvrx_profiler* p, const int32_t* permille, int32_t nq,
+                                int64_t cap_out, int64_t* count, uint32_t* slots, int32_t* num,
+                                float* out) {
+    NVRX_CHECK_ARG(p, "nvrx_profiler_get_quantiles: null handle");
+    if (int rc = check_permille("nvrx_profiler_get_quantiles", permille, nq)) return rc;
+    NVRX_CHECK_ARG(count, "nvrx_profiler_get_quantiles: null count");
+    NVRX_CHECK_ARG(cap_out >= 0, "nvrx_profiler_get_quantiles: negative cap_out");
+    CaptureSelf self(p);  // the call's own kernels are not captured
+    (void)nvrx::capture_flush();
+    std::lock_guard<std::mutex> lk(p->mu);
+    DeviceGuard g(p->cfg.device);
+    int rc = flush_locked(p);
+    if (rc) return rc;
+    *count = 0;
+    const int64_t nslots = (int64_t)p->names.size();
+    if (p->log_n == 0 || nslots == 0) return NVRX_OK;
+    // the work buffer of the bucketing followed by num [nslots] (256-B aligned) and the quantiles
+    // [nq][nslots]: sized before bucket_log so that its own ensure_work keeps the allocation
+    const size_t row = align256((size_t)nslots * 4);
+    const size_t span = row + (size_t)nq * (size_t)nslots * 4;
+    const size_t carve_bytes = carve(nullptr, nslots, nvrx::records_bucket_capacity(p->log_n, 1, nslots)).bytes;
+    rc = ensure_work(p, carve_bytes + span);
+    if (rc) return rc;
+    Work w;
+    rc = bucket_log(p, nslots, 0, w);
+    if (rc) return rc;
+    char* extra = (char*)p->d_work + carve_bytes;
+    const int64_t cap = p->cfg.stats_max_len_per_kernel;
+    hipError_t e = nvrx::segment_quantiles_ragged(w.ns, w.seg_off, w.seg_len, nslots,
+                                                  std::min<int64_t>(cap, p->log_n), cap, true, permille,
+                                                  nq, (float*)(extra + row), (int32_t*)extra, p->stream);
+    if (e != hipSuccess) return hip_status(e, "nvrx_profiler_get_quantiles: segment_quantiles");
+    rc = ensure_small(p, span);
+    if (rc) return rc;
+    e = hipMemcpyAsync(p->h_small, extra, span, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) return hip_status(e, "nvrx_profiler_get_quantiles: download");
+    const int32_t* hnum = (const int32_t*)p->h_small;
+    const float* hq = (const float*)(p->h_small + row);
+    std::vector<uint32_t> order;
+    for (int64_t s = 0; s < nslots; ++s)
+        if (hnum[s] > 0) order.push_back((uint32_t)s);
+    std::sort(order.begin(), order.end(),
+              [&](uint32_t a, uint32_t b) { return p->names[a] < p->names[b]; });
+    *count = (int64_t)order.size();
+    const int64_t m = std::min<int64_t>(cap_out, *count);
+    for (int64_t i = 0; i < m; ++i) {
+        if (slots) slots[i] = order[i];
+        if (num) num[i] = hnum[order[i]];
+        if (out)
+            for (int32_t j = 0; j < nq; ++j) out[j * cap_out + i] = hq[j * nslots + order[i]];
     }
     return NVRX_OK;
 }

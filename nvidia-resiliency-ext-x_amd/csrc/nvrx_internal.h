@@ -20,6 +20,16 @@ hipError_t segment_stats_ragged(const uint32_t* ns, const int64_t* seg_off, cons
                                 bool aligned16, const nvrx_stats_soa& out, uint32_t* col_ref,
                                 int64_t ncols, hipStream_t st);
 
+// tail quantiles (segment_quantiles.hip): out [nq][nseg], num [nseg] or NULL; permille on the host
+hipError_t segment_quantiles_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
+                                     int64_t seg_begin, int64_t seg_len, int64_t cap,
+                                     const int32_t* permille, int nq, float* out, int32_t* num,
+                                     hipStream_t st);
+hipError_t segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off, const int32_t* seg_len,
+                                    int64_t nseg, int64_t max_len, int64_t cap, bool aligned16,
+                                    const int32_t* permille, int nq, float* out, int32_t* num,
+                                    hipStream_t st);
+
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 
 hipError_t kernel_ref(const int32_t* num, const float* med, int64_t R, int64_t K, float* ref,

@@ -27,6 +27,7 @@ NVRX_STATS_FAST = 0
 NVRX_STATS_EXACT = 1
 NVRX_STATS_COLREF_READY = 0x10
 NVRX_MAX_SEGMENT = 1 << 30  # rings above 32,768 samples sort in device scratch
+NVRX_MAX_QUANTILES = 8  # quantiles (permilles) one nvrx_*_quantiles* call resolves
 
 P = ctypes.c_void_p
 i32 = ctypes.c_int32
@@ -87,6 +88,8 @@ SIGNATURES = {
                                                   ctypes.POINTER(StatsSoA), P, i64, P]),
     "nvrx_segment_stats_ragged": (ctypes.c_int, [P, P, P, i64, i64, i64, i32, i32,
                                                  ctypes.POINTER(StatsSoA), P, i64, P]),
+    "nvrx_segment_quantiles_strided": (ctypes.c_int, [P, i64, i64, i64, i64, i64, P, i32, P, P, P]),
+    "nvrx_segment_quantiles_ragged": (ctypes.c_int, [P, P, P, i64, i64, i64, i32, P, i32, P, P, P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),
@@ -114,6 +117,7 @@ SIGNATURES = {
     "nvrx_profiler_get_stats": (ctypes.c_int, [P, i64, ctypes.POINTER(i64), P, P, P, P, P, P, P]),
     "nvrx_profiler_kernel_name": (ctypes.c_int, [P, u32, ctypes.c_char_p, i64]),
     "nvrx_profiler_get_records": (ctypes.c_int, [P, i64, ctypes.POINTER(i64), P]),
+    "nvrx_profiler_get_quantiles": (ctypes.c_int, [P, P, i32, i64, ctypes.POINTER(i64), P, P, P]),
     "nvrx_profiler_capture_available": (ctypes.c_int, []),
     "nvrx_capture_flush": (ctypes.c_int, []),
     "nvrx_capture_stats": (ctypes.c_int, [ctypes.POINTER(CaptureCounters)]),

@@ -232,6 +232,36 @@ class KernelProfiler:
         names = [self._name_of(int(s)) for s in slots]
         return KernelSummaries(names, num, *cols)
 
+    def get_quantiles(self, permille):
+        """Per-kernel duration quantiles (HIP) over the records the rings retain: ``(names, num,
+        q)`` with names sorted, num the retained records per kernel and q a float32 array
+        [len(permille), len(names)] in us.  ``permille``: up to 8 ints in [0, 1000]; entry j asks
+        for the sample of 0-based rank ``(permille[j] * (n - 1)) // 1000`` among a kernel's n sorted
+        durations (no interpolation: 0 is MIN, 1000 MAX, 500 of an odd n the median).  Beyond
+        the reference (CuptiProfiler::getStats stops at the median); it leaves the records and
+        ``get_stats`` as they are, so call it before ``reset``."""
+        from .ops import permille_array
+
+        pm = permille_array(permille)
+        nq = len(pm)
+        L = N.lib()
+        count = ctypes.c_int64()
+        N.check(L.nvrx_profiler_get_quantiles(self._h, pm, nq, 0, ctypes.byref(count), None, None,
+                                              None), "get_quantiles")
+        while True:
+            n = int(count.value)
+            slots = np.empty(n, np.uint32)
+            num = np.empty(n, np.int32)
+            q = np.empty((nq, n), np.float32)
+            N.check(L.nvrx_profiler_get_quantiles(self._h, pm, nq, n, ctypes.byref(count),
+                                                  slots.ctypes.data, num.ctypes.data,
+                                                  q.ctypes.data), "get_quantiles")
+            if int(count.value) <= n:
+                break
+        m = int(count.value)  # may have shrunk (a reset from another thread)
+        names = [self._name_of(int(s)) for s in slots[:m]]
+        return names, num[:m], np.ascontiguousarray(q[:, :m])
+
     def get_records(self):
         """(slots u32, ns u32) of the device record log since the last reset, push order
         (nvrx_profiler_get_records) -- what the statistics are computed from."""
@@ -326,6 +356,12 @@ class CuptiManager:
         with self.lock:
             self._ensure_initialized()
             return self.cupti_ext.get_stats_columns()
+
+    def get_quantiles(self, permille):
+        """``KernelProfiler.get_quantiles`` of the active run: (names, num, q [nq, n])."""
+        with self.lock:
+            self._ensure_initialized()
+            return self.cupti_ext.get_quantiles(permille)
 
     def reset_results(self):
         with self.lock:

@@ -7,6 +7,7 @@ launch (the C layer re-checks).
 from __future__ import annotations
 
 import ctypes
+import numbers
 from dataclasses import dataclass
 from typing import Optional
 
@@ -105,6 +106,80 @@ def segment_stats_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: Optio
     N.call("nvrx_segment_stats_ragged", ns.data_ptr(), seg_off.data_ptr(),
            N.ptr(seg_len), nseg, max_len, cap, mode, int(aligned16), ctypes.byref(soa),
            N.ptr(col_ref), ncols if col_ref is not None else 0, _stream(stream))
+    return out
+
+
+def permille_array(permille):
+    """The quantile requests as the C ABI takes them (a host int32 array): a non-empty
+    sequence of at most ``_native.NVRX_MAX_QUANTILES`` ints in [0, 1000]; ValueError if not."""
+    try:
+        pm = list(permille)
+    except TypeError:
+        raise ValueError("permille must be a sequence of ints in [0, 1000]") from None
+    if not 1 <= len(pm) <= N.NVRX_MAX_QUANTILES:
+        raise ValueError(f"permille must hold 1 to {N.NVRX_MAX_QUANTILES} entries, got {len(pm)}")
+    for v in pm:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= 1000:
+            raise ValueError(f"permille entries must be ints in [0, 1000], got {v!r}")
+    return (ctypes.c_int32 * len(pm))(*(int(v) for v in pm))
+
+
+def _quantile_outputs(nq, nseg, device, out, num):
+    if out is None:
+        out = torch.empty((nq, nseg), dtype=torch.float32, device=device)
+    N.require_device(out, "out")
+    if out.dtype != torch.float32 or tuple(out.shape) != (nq, nseg) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape [nq, nseg]")
+    if num is not None:
+        N.require_device(num, "num")
+        if num.dtype != torch.int32 or num.numel() < nseg or not num.is_contiguous():
+            raise ValueError("num must be a contiguous int32 tensor of >= nseg elements")
+    return out
+
+
+def segment_quantiles_strided(ns: torch.Tensor, nseg: int, seg_stride: int, seg_begin: int,
+                              seg_len: int, permille, cap: int = 0,
+                              out: Optional[torch.Tensor] = None, num: Optional[torch.Tensor] = None,
+                              stream=None) -> torch.Tensor:
+    """Quantiles of the segments of ``segment_stats_strided`` (same addressing, same ring
+    retention).  ``permille``: up to 8 ints in [0, 1000]; row j of the returned [nq, nseg] float32
+    tensor holds, per segment of n retained samples, the sample of 0-based rank
+    ``(permille[j] * (n - 1)) // 1000`` among the sorted duration keys, in us -- a sample, never an
+    interpolation (0 -> MIN, 1000 -> MAX, 500 of an odd n -> MED, bit for bit); NaN for an empty
+    segment.  ``num`` (int32 [nseg], optional) receives the retained lengths."""
+    pm = permille_array(permille)
+    N.require_device(ns, "ns")
+    if ns.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
+    if nseg > 0 and (nseg - 1) * seg_stride + seg_begin + seg_len > ns.numel():
+        raise ValueError("segments exceed the ns tensor")
+    out = _quantile_outputs(len(pm), max(nseg, 0), ns.device, out, num)
+    N.call("nvrx_segment_quantiles_strided", ns.data_ptr(), nseg, seg_stride, seg_begin, seg_len,
+           cap, pm, len(pm), out.data_ptr(), N.ptr(num), _stream(stream))
+    return out
+
+
+def segment_quantiles_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: Optional[torch.Tensor],
+                             max_len: int, permille, cap: int = 0, aligned16: bool = False,
+                             out: Optional[torch.Tensor] = None, num: Optional[torch.Tensor] = None,
+                             stream=None) -> torch.Tensor:
+    """Quantiles of the ragged segments of ``segment_stats_ragged`` ([nq, nseg] float32, as
+    ``segment_quantiles_strided``); every segment is read by its own retained length, a
+    segment with ``seg_len < 0`` is skipped (its outputs untouched)."""
+    pm = permille_array(permille)
+    N.require_device(ns, "ns")
+    N.require_device(seg_off, "seg_off")
+    if ns.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
+    nseg = seg_off.numel() - (0 if seg_len is not None else 1)
+    if seg_off.dtype != torch.int64 or (seg_len is not None and seg_len.dtype != torch.int32):
+        raise TypeError("seg_off must be int64 and seg_len int32")
+    if seg_len is not None:
+        N.require_device(seg_len, "seg_len")
+    out = _quantile_outputs(len(pm), max(nseg, 0), ns.device, out, num)
+    N.call("nvrx_segment_quantiles_ragged", ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len),
+           max(nseg, 0), max_len, cap, int(aligned16), pm, len(pm), out.data_ptr(), N.ptr(num),
+           _stream(stream))
     return out
 
 

@@ -17,7 +17,7 @@ import socket
 import time
 from collections.abc import Callable
 from contextlib import contextmanager
-from typing import Any, Deque, Dict, List, Optional, Sequence, Union
+from typing import Any, Deque, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -148,6 +148,22 @@ class Detector:
     def _get_kernel_summaries(cls):
         """Per-kernel statistics from the device record log (name-sorted mapping)."""
         return cls.cupti_manager.get_results_columns()
+
+    @classmethod
+    def kernel_quantiles(cls, permille: Sequence[int] = (500, 900, 990)) -> Dict[str, Tuple[float, ...]]:
+        """Duration quantiles (us) of every kernel captured in the current report interval:
+        composite kernel name -> one value per entry of ``permille`` (up to 8 ints in
+        [0, 1000]).  Entry pm is the sample of 0-based rank ``(pm * (n - 1)) // 1000`` among the
+        kernel's n retained durations sorted ascending -- a sample, never an interpolation.
+        Beyond the reference: the tail a rank that is slow on every n-th call shows, which its
+        median hides.  Call it BEFORE ``generate_report``, which resets the profiler results
+        (afterwards the interval is empty and this returns {}).  It changes neither the
+        report, nor the scores, nor any collective."""
+        assert cls.initialized
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        names, _, q = cls.cupti_manager.get_quantiles(permille)
+        return {n: tuple(float(x) for x in q[:, i]) for i, n in enumerate(names)}
 
     @classmethod
     def _reset_sections_elapseds(cls):
