@@ -24,6 +24,7 @@ import os
 import time
 import weakref
 from dataclasses import dataclass
+from functools import partial
 from typing import Optional
 
 import numpy as np
@@ -105,6 +106,80 @@ class BatchResult:
     err: int = 0
 
 
+@dataclass(eq=False)
+class _ReportBuffers:
+    """The device buffers of one report: segment statistics, the per-kernel reference the
+    statistics epilogue produces ([min bits | missing]; + its f32 form for the column reduction),
+    the scores epilogue's completion counter, the packed results, on N GPUs the shard's partials
+    and their gathered copy, and the record-stream bucketing scratch (allocated and grown by
+    compute_stats_records).  clean: col_ref holds the initial reference (set by the scores
+    epilogue).  A MatrixReporter owns one set; PipelinedReports adds one per further report in
+    flight.  The class also owns the packed-result layout -- one device-to-host copy per report:
+    [gpu_rel f64 R][gpu_ind f64 R][strag_rel u8 R][strag_ind u8 R][pad][err i32]"""
+    R: int
+    relative: bool
+    individual: bool
+    stats: ops.SegmentStats
+    col_ref: torch.Tensor
+    ref_f32: torch.Tensor
+    # self-resetting scores epilogue (nvrx_score_args.done, zero before the first report): the
+    # scores kernel's last workgroup stores the error bits and re-initialises col_ref for the next
+    # report, so a report is two launches (statistics, scores) with no initialising fill in between
+    done: torch.Tensor
+    out: torch.Tensor
+    partials: torch.Tensor
+    gathered: Optional[torch.Tensor]
+    bucket: Optional[tuple] = None
+    clean: bool = False
+
+    def __post_init__(self):
+        self.err = self.err_of(self.out)
+
+    @classmethod
+    def new(cls, rep: "MatrixReporter") -> "_ReportBuffers":
+        """A fresh set for a reporter: results and completion counter zeroed, the column
+        reference uninitialised (its first statistics phase initialises it), no scratch yet."""
+        R, K, d = rep.R, rep.K, rep.device
+        return cls(R, rep.relative, rep.individual,
+                   stats=ops.SegmentStats.empty(R * K, d),
+                   col_ref=torch.empty(2 * max(K, 1), dtype=torch.int32, device=d),
+                   ref_f32=torch.empty(max(K, 1), dtype=torch.float32, device=d),
+                   done=torch.zeros(2, dtype=torch.int32, device=d),
+                   out=torch.zeros(cls.nbytes(R), dtype=torch.uint8, device=d),
+                   partials=torch.empty((R, 6), dtype=torch.float64, device=d),
+                   gathered=(torch.empty((rep.world, R, 6), dtype=torch.float64, device=d)
+                             if rep.exchange else None))
+
+    @staticmethod
+    def nbytes(R: int) -> int:
+        return (18 * R + 7) // 8 * 8 + 8
+
+    def _split(self, b):
+        """The byte ranges of a packed buffer (a uint8 tensor or numpy array)."""
+        R, e = self.R, self.nbytes(self.R) - 8
+        return b[0:8 * R], b[8 * R:16 * R], b[16 * R:17 * R], b[17 * R:18 * R], b[e:e + 4]
+
+    def views(self, buf: Optional[torch.Tensor] = None) -> dict:
+        """The result arrays inside a packed buffer (default: this set's)."""
+        gr, gi, sr, si, _ = self._split(self.out if buf is None else buf)
+        return dict(gpu_rel=gr.view(torch.float64) if self.relative else None,
+                    gpu_ind=gi.view(torch.float64) if self.individual else None,
+                    strag_rel=sr if self.relative else None,
+                    strag_ind=si if self.individual else None)
+
+    def err_of(self, buf: torch.Tensor) -> torch.Tensor:
+        return self._split(buf)[4].view(torch.int32)
+
+    def unpack(self, buf: torch.Tensor) -> BatchResult:
+        """Host copies of the results in a packed host buffer."""
+        gr, gi, sr, si, err = self._split(buf.numpy())
+        return BatchResult(gr.view(np.float64).copy() if self.relative else None,
+                           gi.view(np.float64).copy() if self.individual else None,
+                           sr.astype(bool) if self.relative else None,
+                           si.astype(bool) if self.individual else None,
+                           int(err.view(np.int32)[0]))
+
+
 class MatrixReporter:
     def __init__(self, R: int, K: int, *, cap: int = 8192, relative: bool = True,
                  individual: bool = True, thr_rel: float = 0.75, thr_ind: float = 0.75,
@@ -127,31 +202,18 @@ class MatrixReporter:
         self.exchange = self.world > 1 if exchange is None else bool(exchange)
         if self.exchange and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
             raise RuntimeError("MatrixReporter(exchange=True) needs an initialized process group")
-        self.stats = ops.SegmentStats.empty(R * K, d)
         self.col_valid = col_valid
-        # per-kernel reference, produced by the stats kernel's epilogue: [min bits | missing]
-        self.col_ref = torch.empty(2 * max(K, 1), dtype=torch.int32, device=d)
-        self._ref_f32 = torch.empty(max(K, 1), dtype=torch.float32, device=d)
+        # the reporter's own buffer set: what every phase below uses unless it is given another
+        # (bufs=); the history and the pinned result buffer are shared by all sets
+        self.own = _ReportBuffers.new(self)
         self.hist = torch.full((R, K), float("inf"), dtype=torch.float32, device=d) if individual else None
-        self.partials = torch.empty((R, 6), dtype=torch.float64, device=d)
-        self.gathered = (torch.empty((self.world, R, 6), dtype=torch.float64, device=d)
-                         if self.exchange else None)
-        # one packed result buffer -> one device-to-host copy per report:
-        # [gpu_rel f64 R][gpu_ind f64 R][strag_rel u8 R][strag_ind u8 R][pad][err i32]
-        self._e = (18 * R + 7) // 8 * 8
-        nbytes = self._e + 8
-        self.out = torch.zeros(nbytes, dtype=torch.uint8, device=d)
-        self.h_out = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        self.views = dict(gpu_rel=self.out[0:8 * R].view(torch.float64),
-                          gpu_ind=self.out[8 * R:16 * R].view(torch.float64),
-                          strag_rel=self.out[16 * R:17 * R], strag_ind=self.out[17 * R:18 * R])
-        self.err = self.out[self._e:self._e + 4].view(torch.int32)
-        # self-resetting scores epilogue (nvrx_score_args.done): the scores kernel's last
-        # workgroup stores the error bits and re-initialises col_ref for the next report, so a
-        # report is two launches (statistics, scores) with no initialising fill in between
-        self.done = torch.zeros(2, dtype=torch.int32, device=d)
-        self._colref_clean = False  # col_ref holds the initial reference (set by the epilogue)
+        self.h_out = torch.empty(_ReportBuffers.nbytes(R), dtype=torch.uint8, pin_memory=True)
         self._pipes = weakref.WeakSet()  # PipelinedReports over this reporter
+
+    @property
+    def stats(self) -> ops.SegmentStats:
+        """The segment statistics of the reporter's own buffer set."""
+        return self.own.stats
 
     def _order_after_inflight(self, exclude=None) -> None:
         """The caller's stream waits for every pipelined report still in flight on this reporter.
@@ -177,43 +239,47 @@ class MatrixReporter:
     def _fuse_ref(self) -> bool:
         return self.relative and self.R <= FUSED_REF_MAX_ROWS
 
-    def _column_ref(self):
+    # (bufs: the buffer set a phase reads and writes; None: the reporter's own)
+    def _column_ref(self, bufs: Optional[_ReportBuffers] = None):
         """Per-kernel reference by a separate column reduction into the col_ref layout."""
+        b = self.own if bufs is None else bufs
         if self.relative and not self._fuse_ref():
-            st = self.stats.view(self.R, self.K)
-            ops.kernel_ref(st.num, st.med, ref=self._ref_f32, scratch=self.col_ref)
+            st = b.stats.view(self.R, self.K)
+            ops.kernel_ref(st.num, st.med, ref=b.ref_f32, scratch=b.col_ref)
 
-    def compute_stats(self, ns: torch.Tensor, s_push: int) -> ops.SegmentStats:
+    def compute_stats(self, ns: torch.Tensor, s_push: int,
+                      bufs: Optional[_ReportBuffers] = None) -> ops.SegmentStats:
         # (inside a graph capture the flag describes the device state when the graph replays:
         # the captured sequences always pair a statistics call with the scores that follow)
+        b = self.own if bufs is None else bufs
         self._order_after_inflight()
         st = ops.segment_stats_strided(ns.view(-1), self.R * self.K, s_push, 0, s_push,
-                                       cap=self.cap, mode=self.mode, out=self.stats,
-                                       col_ref=self.col_ref if self._fuse_ref() else None,
-                                       ncols=self.K, colref_ready=self._colref_clean)
-        self._colref_clean = False
-        self._column_ref()
+                                       cap=self.cap, mode=self.mode, out=b.stats,
+                                       col_ref=b.col_ref if self._fuse_ref() else None,
+                                       ncols=self.K, colref_ready=b.clean)
+        b.clean = False
+        self._column_ref(b)
         return st
 
-    def compute_stats_records(self, recs: torch.Tensor, rec_off: torch.Tensor) -> ops.SegmentStats:
+    def compute_stats_records(self, recs: torch.Tensor, rec_off: torch.Tensor,
+                              bufs: Optional[_ReportBuffers] = None) -> ops.SegmentStats:
         """recs [n, 2] int32 {slot, ns} of R streams (rec_off [R+1] int64, device): the
         reference's ring pushes (CuptiProfiler.cpp:168-203) + getStats, for every rank."""
+        b = self.own if bufs is None else bufs
         self._order_after_inflight()
         n = recs.shape[0]
         need = ops.records_bucket_capacity(n, self.R, self.K)
-        b = getattr(self, "_bucket", None)
-        if b is None or b[2].numel() < need:
+        if b.bucket is None or b.bucket[2].numel() < need:
             d = self.device
             # (no per-bucket push counts: a report needs the kept records only)
-            b = (torch.empty(self.R * self.K, dtype=torch.int64, device=d),
-                 torch.empty(self.R * self.K, dtype=torch.int32, device=d),
-                 torch.empty(max(need, 1), dtype=torch.int32, device=d), None)
-            self._bucket = b
+            b.bucket = (torch.empty(self.R * self.K, dtype=torch.int64, device=d),
+                        torch.empty(self.R * self.K, dtype=torch.int32, device=d),
+                        torch.empty(max(need, 1), dtype=torch.int32, device=d), None)
         max_len = min(self.cap, n) if self.cap > 0 else n
-        self._colref_clean = False
+        b.clean = False
         return ops.records_stats(recs, rec_off, self.K, self.cap, max(max_len, 1), mode=self.mode,
-                                 out=self.stats, bucket=b,
-                                 col_ref=self.col_ref if self.relative else None)
+                                 out=b.stats, bucket=b.bucket,
+                                 col_ref=b.col_ref if self.relative else None)
 
     def report_records(self, recs: torch.Tensor, rec_off: torch.Tensor) -> BatchResult:
         """One full report from record streams resident in HBM."""
@@ -221,82 +287,72 @@ class MatrixReporter:
         self.compute_scores()
         return self.land()
 
-    def _outputs(self, buf: Optional[torch.Tensor] = None):
-        R = self.R
-        b = self.out if buf is None else buf
-        return dict(gpu_rel=b[0:8 * R].view(torch.float64) if self.relative else None,
-                    gpu_ind=b[8 * R:16 * R].view(torch.float64) if self.individual else None,
-                    strag_rel=b[16 * R:17 * R] if self.relative else None,
-                    strag_ind=b[17 * R:18 * R] if self.individual else None,
-                    thr_rel=self.thr_rel, thr_ind=self.thr_ind, round_f32=self.round_f32)
-
-    def compute_scores(self, out_buf: Optional[torch.Tensor] = None) -> None:
-        """Scores + straggler masks into the packed buffer (one kernel on 1 GPU; partials ->
-        RCCL all_gather -> finalize on N GPUs).  out_buf: another packed buffer of the same
-        layout (1 GPU), e.g. pinned host memory the kernel writes directly (no copy)."""
-        R, K = self.R, self.K
-        self._order_after_inflight()
-        st = self.stats.view(R, K)
-        ref = self.col_ref.view(torch.float32)[:K] if self.relative else None
-        missing = self.col_ref[K:2 * K] if self.relative else None
+    def _scores(self, b: _ReportBuffers, err: torch.Tensor, **into) -> None:
+        """The scores kernel over set b's statistics and reference; into: finalize= (1 GPU) or
+        partials= (N GPUs)."""
+        K = self.K
+        st = b.stats.view(self.R, K)
         # the self-resetting epilogue where the per-kernel reference is fused into the
         # statistics (R <= FUSED_REF_MAX_ROWS): one completion counter per report, whose
         # same-address atomics would cost ~0.15 / 1 ms at 4,096 / 16,384 rows
         fused = self._fuse_ref()
-        reset = self.col_ref[:2 * K] if fused else None
-        done = self.done if fused else None
+        if not fused:
+            err.zero_()
+        ops.scores(st.num, st.med, st.avg, col_valid=self.col_valid,
+                   ref=b.col_ref.view(torch.float32)[:K] if self.relative else None,
+                   ref_missing=b.col_ref[K:2 * K] if self.relative else None,
+                   hist=self.hist, err=err, done=b.done if fused else None,
+                   reset_col_ref=b.col_ref[:2 * K] if fused else None, **into)
+        b.clean = fused
+
+    def compute_scores(self, out_buf: Optional[torch.Tensor] = None,
+                       bufs: Optional[_ReportBuffers] = None) -> None:
+        """Scores + straggler masks into the packed buffer (one kernel on 1 GPU; partials ->
+        RCCL all_gather -> finalize on N GPUs).  out_buf: another packed buffer of the same
+        layout (1 GPU), e.g. pinned host memory the kernel writes directly (no copy)."""
+        b = self.own if bufs is None else bufs
+        self._order_after_inflight()
         if not self.exchange:
-            b = self.out if out_buf is None else out_buf
-            err = b[self._e:self._e + 4].view(torch.int32)
-            if not fused:
-                err.zero_()
-            ops.scores(st.num, st.med, st.avg, col_valid=self.col_valid, ref=ref,
-                       ref_missing=missing, hist=self.hist, err=err,
-                       finalize=self._outputs(b), done=done, reset_col_ref=reset)
-            self._colref_clean = fused
+            self._scores(b, b.err if out_buf is None else b.err_of(out_buf),
+                         finalize=dict(b.views(out_buf), thr_rel=self.thr_rel, thr_ind=self.thr_ind,
+                                       round_f32=self.round_f32))
             return
-        self._scores_partials()
-        self._exchange()
-        self._finalize()
+        self._scores_partials(b)
+        self._exchange(b)
+        self._finalize(b)
 
     # -- the N-GPU scoring in three phases: per-rank partials of this shard's kernels (HIP), the
     # all_gather of the partials (RCCL / gloo), the combine in shard order (HIP) --
-    def _scores_partials(self) -> None:
-        R, K = self.R, self.K
-        st = self.stats.view(R, K)
-        ref = self.col_ref.view(torch.float32)[:K] if self.relative else None
-        missing = self.col_ref[K:2 * K] if self.relative else None
-        fused = self._fuse_ref()
-        if not fused:
-            self.err.zero_()
-        ops.scores(st.num, st.med, st.avg, col_valid=self.col_valid, ref=ref,
-                   ref_missing=missing, hist=self.hist, partials=self.partials, err=self.err,
-                   done=self.done if fused else None,
-                   reset_col_ref=self.col_ref[:2 * K] if fused else None)
-        self._colref_clean = fused
+    def _scores_partials(self, bufs: Optional[_ReportBuffers] = None) -> None:
+        b = self.own if bufs is None else bufs
+        self._scores(b, b.err, partials=b.partials)
 
-    def _exchange(self) -> None:
+    def _exchange(self, bufs: Optional[_ReportBuffers] = None) -> None:
+        b = self.own if bufs is None else bufs
         R = self.R
-        flat = self.gathered.view(self.world * R, 6)
+        flat = b.gathered.view(self.world * R, 6)
         if self.gloo:  # gloo collectives take host tensors
             hg = torch.empty((self.world * R, 6), dtype=torch.float64)
-            torch.distributed.all_gather_into_tensor(hg, self.partials.cpu(), group=self.group)
+            torch.distributed.all_gather_into_tensor(hg, b.partials.cpu(), group=self.group)
             flat.copy_(hg)
         else:          # RCCL over xGMI, device to device
-            torch.distributed.all_gather_into_tensor(flat, self.partials, group=self.group)
+            torch.distributed.all_gather_into_tensor(flat, b.partials, group=self.group)
 
-    def _finalize(self) -> None:
-        R = self.R
-        o = self._outputs()
-        ops.finalize_scores(self.gathered, R, self.world, self.round_f32, self.thr_rel,
-                            self.thr_ind, rel=self.relative, ind=self.individual, err=self.err,
-                            out={k: o[k] for k in ("gpu_rel", "gpu_ind", "strag_rel", "strag_ind")})
+    def _finalize(self, bufs: Optional[_ReportBuffers] = None) -> None:
+        b = self.own if bufs is None else bufs
+        ops.finalize_scores(b.gathered, self.R, self.world, self.round_f32, self.thr_rel,
+                            self.thr_ind, rel=self.relative, ind=self.individual, err=b.err,
+                            out=b.views())
 
-    def land(self) -> BatchResult:
+    def _copy_out(self, host: torch.Tensor, bufs: Optional[_ReportBuffers] = None) -> None:
+        """The one device-to-host copy of a set's packed results, into a pinned buffer."""
+        host.copy_((self.own if bufs is None else bufs).out, non_blocking=True)
+
+    def land(self, bufs: Optional[_ReportBuffers] = None) -> BatchResult:
         """The one device-to-host copy of the packed results, then host views."""
-        self.h_out.copy_(self.out, non_blocking=True)
+        self._copy_out(self.h_out, bufs)
         _wait(self.device)
-        return self._unpack()
+        return self.own.unpack(self.h_out)
 
     def report(self, ns: torch.Tensor, s_push: int) -> BatchResult:
         """One full report: samples resident in HBM -> scores + straggler sets on host."""
@@ -313,7 +369,8 @@ class MatrixReporter:
 
     def graph_records(self, recs: torch.Tensor, rec_off: torch.Tensor) -> "ReportGraph":
         """graph() over record streams resident in HBM (compute_stats_records captured)."""
-        return ReportGraph(self, None, 0, stats=lambda: self.compute_stats_records(recs, rec_off))
+        return ReportGraph(self, None, 0, stats=lambda bufs: self.compute_stats_records(
+            recs, rec_off, bufs=bufs))
 
     def pipelined(self, ns, s_push: int, timing: bool = False,
                   mode: Optional[str] = None, depth: int = 2,
@@ -326,35 +383,27 @@ class MatrixReporter:
         a report that reads it is in flight: collect() raises if a torch in-place operation
         changed it (its version counter moved) between that report's submit() and collect()."""
         ins = list(ns) if isinstance(ns, (list, tuple)) else [ns]
-        return PipelinedReports(self, None, s_push, timing, mode=mode, depth=depth,
-                                timing_reps=timing_reps,
-                                stats=[lambda x=x: self.compute_stats(x, s_push) for x in ins],
-                                stats_bytes=self._matrix_bytes(s_push), inputs=[(x,) for x in ins])
+        return PipelinedReports(
+            self, [lambda bufs, x=x: self.compute_stats(x, s_push, bufs=bufs) for x in ins],
+            inputs=[(x,) for x in ins], stats_bytes=self._matrix_bytes(s_push), timing=timing,
+            mode=mode, depth=depth, timing_reps=timing_reps)
 
     def _matrix_bytes(self, s_push: int) -> int:
         keep = min(s_push, self.cap) if self.cap > 0 else s_push
         return 4 * self.R * self.K * keep  # 4 B per retained sample
 
     def pipelined_records(self, recs, rec_off: torch.Tensor, timing: bool = False,
-                          mode: Optional[str] = None, timing_reps: int = 1) -> "PipelinedReports":
+                          mode: Optional[str] = None, depth: int = 2,
+                          timing_reps: int = 1) -> "PipelinedReports":
         """pipelined() over record streams resident in HBM (compute_stats_records: bucketing,
         classification and the class kernels -- side-stream fork / join and stream-ordered
         scratch included -- captured into the report graphs).  recs: one record tensor or a list
         of them (same layout, rec_off shared), as ns for pipelined()."""
         ins = list(recs) if isinstance(recs, (list, tuple)) else [recs]
-        return PipelinedReports(self, None, 0, timing, mode=mode, stats_bytes=8 * ins[0].shape[0],
-                                timing_reps=timing_reps,
-                                stats=[lambda r=r: self.compute_stats_records(r, rec_off) for r in ins],
-                                inputs=[(r, rec_off) for r in ins])
-
-    def _unpack(self, buf: Optional[torch.Tensor] = None) -> BatchResult:
-        R = self.R
-        h = (self.h_out if buf is None else buf).numpy()
-        gr = h[0:8 * R].view(np.float64).copy() if self.relative else None
-        gi = h[8 * R:16 * R].view(np.float64).copy() if self.individual else None
-        sr = h[16 * R:17 * R].astype(bool) if self.relative else None
-        si = h[17 * R:18 * R].astype(bool) if self.individual else None
-        return BatchResult(gr, gi, sr, si, int(h[self._e:self._e + 4].view(np.int32)[0]))
+        return PipelinedReports(
+            self, [lambda bufs, r=r: self.compute_stats_records(r, rec_off, bufs=bufs) for r in ins],
+            inputs=[(r, rec_off) for r in ins], stats_bytes=8 * ins[0].shape[0], timing=timing,
+            mode=mode, depth=depth, timing_reps=timing_reps)
 
 
 class ReportGraph:
@@ -368,64 +417,55 @@ class ReportGraph:
 
     def __init__(self, rep: MatrixReporter, ns: Optional[torch.Tensor], s_push: int, stats=None):
         self.rep = rep
+        own = rep.own  # the graphs run over the reporter's own buffer set
         if stats is None:  # the statistics phase (record streams: MatrixReporter.graph_records)
-            stats = lambda: rep.compute_stats(ns, s_push)  # noqa: E731
+            stats = lambda bufs: rep.compute_stats(ns, s_push, bufs=bufs)  # noqa: E731
         _warm_up(rep, stats)
         # the captured statistics phase trusts col_ref as the previous report's scores epilogue
         # left it (colref_ready at capture): replays must pair it with the scores (run_rest),
         # which run_stats checks against the reporter's flag -- kept current by every replay
-        self._needs_clean = rep._colref_clean
-        self.stats = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.stats):
-            stats()
+        self._needs_clean = own.clean
+        stats, copy_out = partial(stats, own), partial(rep._copy_out, rep.h_out)
+        self.stats = _capture(stats)
         self.rest = self.full = None
         if rep.exchange:
             # N GPUs: the shard's partials and the combine (+ the result copy) as graphs too;
             # only the all_gather of the partials between them runs eagerly
-            self.partials = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.partials):
-                rep._scores_partials()
-            self.finalize = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.finalize):
-                rep._finalize()
-                rep.h_out.copy_(rep.out, non_blocking=True)
+            self.partials = _capture(rep._scores_partials)
+            self.finalize = _capture(rep._finalize, copy_out)
         else:
-            self.rest = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.rest):
-                rep.compute_scores()
-                rep.h_out.copy_(rep.out, non_blocking=True)
-            self.full = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.full):
-                stats()
-                rep.compute_scores()
-                rep.h_out.copy_(rep.out, non_blocking=True)
+            self.rest = _capture(rep.compute_scores, copy_out)
+            self.full = _capture(stats, rep.compute_scores, copy_out)
 
     def _check_clean(self) -> None:
-        if self._needs_clean and not self.rep._colref_clean:
+        if self._needs_clean and not self.rep.own.clean:
             raise RuntimeError("ReportGraph: the statistics graph was captured to follow a scores "
                                "phase (its epilogue re-initialises the column reference); the last "
                                "statistics phase was not followed by run_rest()")
+
+    def _finish(self) -> BatchResult:
+        """After the scores were replayed: the flag, the wait, the host views."""
+        rep = self.rep
+        rep.own.clean = rep._fuse_ref()
+        _wait(rep.device)
+        return rep.own.unpack(rep.h_out)
 
     def run_stats(self) -> None:
         self._check_clean()
         self.rep._order_after_inflight()
         self.stats.replay()
-        self.rep._colref_clean = False
+        self.rep.own.clean = False
 
     def run_rest(self) -> BatchResult:
         rep = self.rep
         rep._order_after_inflight()
         if self.rest is None:  # N GPUs: partials graph, eager all_gather, combine graph
             self.partials.replay()
-            rep._colref_clean = rep._fuse_ref()
             rep._exchange()
             self.finalize.replay()
-            _wait(rep.device)
-            return rep._unpack()
-        self.rest.replay()
-        rep._colref_clean = rep._fuse_ref()
-        _wait(rep.device)
-        return rep._unpack()
+        else:
+            self.rest.replay()
+        return self._finish()
 
     def run(self) -> BatchResult:
         if self.full is None:
@@ -434,38 +474,43 @@ class ReportGraph:
         self._check_clean()
         self.rep._order_after_inflight()
         self.full.replay()
-        self.rep._colref_clean = self.rep._fuse_ref()
-        _wait(self.rep.device)
-        return self.rep._unpack()
+        return self._finish()
 
 
-def _warm_up(rep: MatrixReporter, stats) -> None:
-    """One eager report on a side stream (first-launch setup outside any graph capture);
-    stats() runs the statistics phase.  The individual history is restored afterwards: the
-    warm-up must not fold whatever the inputs hold now into it (the graphs' reports advance it
-    exactly as report() does)."""
+def _capture(*phases) -> torch.cuda.CUDAGraph:
+    """The phases (callables), run in order on the current stream, captured as one HIP graph."""
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for phase in phases:
+            phase()
+    return g
+
+
+def _warm_up(rep: MatrixReporter, stats, bufs: Optional[_ReportBuffers] = None) -> None:
+    """One eager report over a buffer set (None: the reporter's own) on a side stream
+    (first-launch setup outside any graph capture); stats(bufs) runs the statistics phase.  The
+    individual history is restored afterwards: the warm-up must not fold whatever the inputs hold
+    now into it (the graphs' reports advance it exactly as report() does)."""
     d = rep.device
+    b = rep.own if bufs is None else bufs
     rep._order_after_inflight()
     saved = rep.hist.clone() if rep.hist is not None else None
     side = torch.cuda.Stream(d)
     side.wait_stream(torch.cuda.current_stream(d))
     with torch.cuda.stream(side):
-        stats()
+        stats(b)
         if not rep.exchange:
-            rep.compute_scores()
+            rep.compute_scores(bufs=b)
         elif rep._fuse_ref():  # N GPUs: leave col_ref initialised without the exchange
-            rep.col_ref[:rep.K].fill_(0x7F800000)
-            rep.col_ref[rep.K:2 * rep.K].zero_()
-            rep._colref_clean = True
+            b.col_ref[:rep.K].fill_(0x7F800000)
+            b.col_ref[rep.K:2 * rep.K].zero_()
+            b.clean = True
         if saved is not None:
             rep.hist.copy_(saved)
     torch.cuda.current_stream(d).wait_stream(side)
     torch.cuda.synchronize(d)
 
 
-# NVRX_PIPE_D2H=copy: pipelined reports write a device buffer and copy it to the pinned one
-# (one more graph node) instead of the scores kernel writing pinned host memory directly
-_PIPE_COPY = os.environ.get("NVRX_PIPE_D2H", "") == "copy"
 # NVRX_PIPE_MODE (timing A/B; PipelinedReports(mode=...) overrides the default, "auto"): "alt" each
 # report on its own stream of two; "side" the statistics phases on one stream, the rest of every
 # report on another; "whole" one whole-report graph per report on the caller's stream (round 4)
@@ -490,59 +535,13 @@ def _spin(cycles: int) -> None:
         spin(int(cycles))
 
 
-class _Slot:
-    """The buffers of one report in flight: segment statistics, column reference (+ its f32
-    form), the scores epilogue's completion counter, the record-stream bucketing output, the
-    packed results (+ error word) and, on N GPUs, the shard's partials and their gathered copy.
-    Slot 0 is the reporter's own set; `clean` mirrors MatrixReporter._colref_clean for this
-    slot's column reference."""
-
-    _FIELDS = ("stats", "col_ref", "_ref_f32", "done", "_bucket", "out", "err", "partials", "gathered")
-
-    def __init__(self, rep: MatrixReporter, primary: bool):
-        self.primary = primary
-        if primary:
-            self.vals = [getattr(rep, f, None) for f in _Slot._FIELDS]
-            self.clean = rep._colref_clean
-        else:
-            out = torch.zeros_like(rep.out)
-            self.vals = [ops.SegmentStats.empty(rep.R * rep.K, rep.device), torch.empty_like(rep.col_ref),
-                         torch.empty_like(rep._ref_f32), torch.zeros_like(rep.done), None, out,
-                         out[rep._e:rep._e + 4].view(torch.int32), torch.empty_like(rep.partials),
-                         torch.empty_like(rep.gathered) if rep.gathered is not None else None]
-            self.clean = False  # uninitialised: its first statistics phase initialises it
-
-    def bind(self, rep: MatrixReporter):
-        """Context: rep's buffers are this slot's (graph capture bakes them into the kernels; the
-        eager exchange reads and writes them)."""
-        slot = self
-
-        class _Bound:
-            def __enter__(self):
-                self.saved = [getattr(rep, f, None) for f in _Slot._FIELDS] + [rep._colref_clean]
-                for f, v in zip(_Slot._FIELDS, slot.vals):
-                    setattr(rep, f, v)
-                rep._colref_clean = slot.clean
-
-            def __exit__(self, *exc):
-                slot.clean = rep._colref_clean
-                slot.vals = [getattr(rep, f, None) for f in _Slot._FIELDS]  # a bucket allocated inside
-                restore = slot.vals if slot.primary else self.saved[:-1]
-                for f, v in zip(_Slot._FIELDS, restore):
-                    setattr(rep, f, v)
-                rep._colref_clean = slot.clean if slot.primary else self.saved[-1]
-                return False
-
-        return _Bound()
-
-
 class PipelinedReports:
     """Full reports as HIP graphs, two in flight.  Each report -- column-reference init,
     statistics, scores + straggler masks -- ends with its packed results landing in one of two
     pinned host buffers, so the host can read report i while report i+1 runs: the GPU sees
     back-to-back reports instead of one report per host round trip.
     mode "alt": report i runs on stream i % 2 with its own set of statistics / reference
-    buffers (_Slot), so report i+1's statistics kernel starts while report i's drains instead of
+    buffers (_ReportBuffers; set 0 is the reporter's own), so report i+1's statistics kernel starts while report i's drains instead of
     after it (the launch-to-launch transition of one stream); report i's scores wait for report
     i-1's, so the individual history advances in submission order.  "side": every statistics
     phase on one stream, every rest on another (buffer sets per report in flight as in alt).
@@ -562,28 +561,23 @@ class PipelinedReports:
     graph holds the statistics phase n times back to back (same inputs and outputs each time) and
     collect() returns the mean per phase, so the events' own overhead and a graph launch are spread
     over n phases.
-    stats: the statistics phase as a callable, or a list of them, one per input set (report i
-    runs stats[i % len(stats)]; default: compute_stats(ns, s_push); record streams:
-    MatrixReporter.pipelined_records).  inputs: per input set, the tensors its statistics phase
+    stats: the statistics phase as a callable stats(bufs) over a buffer set, or a list of them,
+    one per input set (report i runs stats[i % len(stats)]; MatrixReporter.pipelined and
+    pipelined_records build them).  stats_bytes: what one statistics phase reads (the mode
+    choice and the stagger).  inputs: per input set, the tensors its statistics phase
     reads; collect() raises if one of them was modified in place by torch while the report was
     in flight.
     Other work on the same reporter (report(), a ReportGraph, compute_stats, reset_history)
     issued before collect() is ordered after the reports in flight
     (MatrixReporter._order_after_inflight)."""
 
-    def __init__(self, rep: MatrixReporter, ns: Optional[torch.Tensor], s_push: int,
-                 timing: bool = False, stats=None, mode: Optional[str] = None,
-                 timing_reps: int = 1,
-                 stats_bytes: Optional[int] = None, depth: int = 2, inputs=None):
+    def __init__(self, rep: MatrixReporter, stats, *, inputs, stats_bytes: int,
+                 timing: bool = False, mode: Optional[str] = None, depth: int = 2,
+                 timing_reps: int = 1):
         self.mode = mode or _PIPE_MODE or "auto"
-        if stats_bytes is None:  # the matrix path: 4 B per retained sample
-            stats_bytes = rep._matrix_bytes(s_push)
-        if stats is None:
-            stats = [lambda: rep.compute_stats(ns, s_push)]  # noqa: E731
-            inputs = [(ns,)] if inputs is None else inputs
-        elif callable(stats):
+        if callable(stats):
             stats = [stats]
-        self.inputs = list(inputs) if inputs is not None else [() for _ in stats]
+        self.inputs = list(inputs)
         if len(self.inputs) != len(stats) or depth % len(stats) != 0:
             raise ValueError(f"pipelined reports: {len(stats)} input sets for depth {depth} "
                              "(one inputs entry per set; the set count divides depth)")
@@ -609,63 +603,56 @@ class PipelinedReports:
         self.timing_reps = timing_reps
         self.bufs = [torch.zeros_like(rep.h_out).pin_memory() for _ in range(depth)]
 
-        def scores(k: int):
+        # the buffer set of each report in flight: with two streams one per report, the first the
+        # reporter's own; whole reports on one stream all use the reporter's own
+        self.slots = [rep.own] + [_ReportBuffers.new(rep) if self.alt else rep.own
+                                  for _ in range(depth - 1)]
+
+        def run_stats(k: int, reps: int = 1):
+            b = self.slots[k]
+            ready = b.clean
+            for _ in range(reps):
+                # a repeated phase reads the same inputs: the fused reference the previous one
+                # left is the same minimum, so it needs no re-initialisation either
+                b.clean = ready
+                stats[k % len(stats)](b)
+
+        def run_scores(k: int):
             # the scores kernel writes the pinned buffer itself when its epilogue stores the
             # error word (fused reference, R <= FUSED_REF_MAX_ROWS); otherwise the error word is
             # zeroed on the device first and the results copied
-            if _PIPE_COPY or not rep._fuse_ref():
-                rep.compute_scores()
-                self.bufs[k].copy_(rep.out, non_blocking=True)
+            if rep._fuse_ref():
+                rep.compute_scores(out_buf=self.bufs[k], bufs=self.slots[k])
             else:
-                rep.compute_scores(out_buf=self.bufs[k])
-
-        def capture(with_stats: bool, rest: bool, k: int, reps: int = 1):
-            g = torch.cuda.CUDAGraph()
-            ready = rep._colref_clean
-            with torch.cuda.graph(g):
-                for i in range(reps if with_stats else 0):
-                    # a repeated phase reads the same inputs: the fused reference the previous one
-                    # left is the same minimum, so it needs no re-initialisation either
-                    rep._colref_clean = ready
-                    stats[k % len(stats)]()
-                if rest:
-                    scores(k)
-            return g
-
-        def capture_fn(fn):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            return g
+                rep.compute_scores(bufs=self.slots[k])
+                rep._copy_out(self.bufs[k], self.slots[k])
 
         if self.alt:
-            self.slots = [_Slot(rep, True)] + [_Slot(rep, False) for _ in range(depth - 1)]
             self.stats_g, self.rest_g, self.part_g, self.fin_g, self.stats_t = [], [], [], [], []
-            for k, slot in enumerate(self.slots):
-                with slot.bind(rep):
-                    _warm_up(rep, stats[k % len(stats)])  # initialises this slot's column reference too
-                    ready = rep._colref_clean
-                    self.stats_g.append(capture(True, False, k))
-                    if timing:  # the timed statistics phase, timing_reps times in one graph,
-                        rep._colref_clean = ready  # replacing stats_g in a timed report
-                        self.stats_t.append(capture(True, False, k, self.timing_reps))
-                    if rep.exchange:  # N GPUs: partials | eager all_gather | combine + result copy
-                        self.part_g.append(capture_fn(rep._scores_partials))
-                        self.fin_g.append(capture_fn(lambda k=k: (
-                            rep._finalize(), self.bufs[k].copy_(rep.out, non_blocking=True))))
-                    else:
-                        self.rest_g.append(capture(False, True, k))
-            self._needs_clean = rep._colref_clean
+            for k, b in enumerate(self.slots):
+                _warm_up(rep, stats[k % len(stats)], b)  # initialises this set's column reference too
+                ready = b.clean
+                self.stats_g.append(_capture(partial(run_stats, k)))
+                if timing:  # the timed statistics phase, timing_reps times in one graph,
+                    b.clean = ready  # replacing stats_g in a timed report
+                    self.stats_t.append(_capture(partial(run_stats, k, self.timing_reps)))
+                if rep.exchange:  # N GPUs: partials | eager all_gather | combine + result copy
+                    self.part_g.append(_capture(partial(rep._scores_partials, b)))
+                    self.fin_g.append(_capture(partial(rep._finalize, b),
+                                               partial(rep._copy_out, self.bufs[k], b)))
+                else:
+                    self.rest_g.append(_capture(partial(run_scores, k)))
+            self._needs_clean = rep.own.clean
             self.streams = [torch.cuda.Stream(rep.device) for _ in range(depth)]
             self.hist_done = [torch.cuda.Event() for _ in range(depth)]
             self.stats_done = [torch.cuda.Event() for _ in range(depth)]
         else:
             _warm_up(rep, stats[0])
-            self._needs_clean = rep._colref_clean  # as ReportGraph: every graph here pairs both phases
-            self.full = [capture(True, True, k) for k in range(2)]
+            self._needs_clean = rep.own.clean  # as ReportGraph: every graph here pairs both phases
+            self.full = [_capture(partial(run_stats, k), partial(run_scores, k)) for k in range(2)]
             if timing:
-                self.stats = capture(True, False, 0, self.timing_reps)
-                self.rest = [capture(False, True, k) for k in range(2)]
+                self.stats = _capture(partial(run_stats, 0, self.timing_reps))
+                self.rest = [_capture(partial(run_scores, k)) for k in range(2)]
         if timing:
             self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         # blocking-sync events: wait_event's fallback sleeps instead of polling
@@ -686,7 +673,7 @@ class PipelinedReports:
         """Queue the next report (at most `depth` in flight: collect() the oldest first)."""
         if len(self.pending) == self.depth:
             raise RuntimeError(f"{self.depth} reports in flight: collect() one first")
-        if self._needs_clean and not self.rep._colref_clean:
+        if self._needs_clean and not self.rep.own.clean:
             raise RuntimeError("PipelinedReports: an unpaired statistics phase (ReportGraph."
                                "run_stats without run_rest) left the column reference in use")
         if timed and not self.timing:
@@ -703,63 +690,68 @@ class PipelinedReports:
             # latency ahead of it
             _spin(TIMED_SPIN_CYCLES)
         if self.alt:
-            # alt: report i on stream i % 2; side: every statistics phase on stream 0, every rest
-            # on stream 1 (slot k's previous report has finished with its buffers: done[k])
-            s = self.streams[k] if self.mode == "alt" else self.streams[0]
-            # the caller's work so far (inputs; the wait for the collected reports) comes first
-            s.wait_stream(torch.cuda.current_stream(self.rep.device))
-            s.wait_event(self.done[k])
-            if self.mode == "alt" and self.depth > 2:
-                # at most two statistics phases at once: report i's starts on the device as soon
-                # as report i-2's has finished, with no host round trip in between
-                s.wait_event(self.stats_done[(k - 2) % self.depth])
-            if (self.mode == "alt" and self.stagger_cycles > 0 and len(self.pending) == 1
-                    and self.n == self._burst + 1):
-                # the second report of a burst (the pipeline was empty when the first was
-                # submitted) starts a quarter of a statistics phase after the first: staggered,
-                # one report's statistics kernel covers the other's end, scores and the host's
-                # next submission; started together, the two stay locked and the device idles at
-                # every pair's end
-                with torch.cuda.stream(s):
-                    _spin(self.stagger_cycles)
-            with torch.cuda.stream(s):
-                if timed:
-                    self.ev[0].record(s)
-                (self.stats_t[k] if timed else self.stats_g[k]).replay()
-                if timed:
-                    self.ev[1].record(s)
-            self.stats_done[k].record(s)
-            if self.mode == "side":
-                s = self.streams[1]
-                s.wait_event(self.stats_done[k])
-            with torch.cuda.stream(s):
-                s.wait_event(self.hist_done[(k - 1) % self.depth])  # report i-1's history update first
-                if self.rep.exchange:
-                    self.part_g[k].replay()
-                    self.hist_done[k].record(s)
-                    # the eager all_gather of this slot's partials, ordered after them on s (every
-                    # rank submits its reports, hence its collectives, in the same order)
-                    with self.slots[k].bind(self.rep):
-                        self.rep._exchange()
-                    self.fin_g[k].replay()
-                else:
-                    self.rest_g[k].replay()
-                    self.hist_done[k].record(s)
-            self.done[k].record(s)
+            self._submit_two_streams(k, timed)
         else:
-            if timed:
-                self.ev[0].record()
-                self.stats.replay()
-                self.ev[1].record()
-                self.rest[k].replay()
-            else:
-                self.full[k].replay()
-            self.done[k].record()
-        self.rep._colref_clean = self.rep._fuse_ref()
+            self._submit_whole(k, timed)
+        self.rep.own.clean = self.rep._fuse_ref()
         if not self.pending:
             self._burst = self.n  # the first report of a burst (submitted to an empty pipeline)
         self.pending.append((k, self.timing_reps if timed else 0))
         self.n += 1
+
+    def _submit_two_streams(self, k: int, timed: bool) -> None:
+        # alt: report i on stream i % 2; side: every statistics phase on stream 0, every rest
+        # on stream 1 (slot k's previous report has finished with its buffers: done[k])
+        s = self.streams[k] if self.mode == "alt" else self.streams[0]
+        # the caller's work so far (inputs; the wait for the collected reports) comes first
+        s.wait_stream(torch.cuda.current_stream(self.rep.device))
+        s.wait_event(self.done[k])
+        if self.mode == "alt" and self.depth > 2:
+            # at most two statistics phases at once: report i's starts on the device as soon
+            # as report i-2's has finished, with no host round trip in between
+            s.wait_event(self.stats_done[(k - 2) % self.depth])
+        if (self.mode == "alt" and self.stagger_cycles > 0 and len(self.pending) == 1
+                and self.n == self._burst + 1):
+            # the second report of a burst (the pipeline was empty when the first was
+            # submitted) starts a quarter of a statistics phase after the first: staggered,
+            # one report's statistics kernel covers the other's end, scores and the host's
+            # next submission; started together, the two stay locked and the device idles at
+            # every pair's end
+            with torch.cuda.stream(s):
+                _spin(self.stagger_cycles)
+        with torch.cuda.stream(s):
+            if timed:
+                self.ev[0].record(s)
+            (self.stats_t[k] if timed else self.stats_g[k]).replay()
+            if timed:
+                self.ev[1].record(s)
+        self.stats_done[k].record(s)
+        if self.mode == "side":
+            s = self.streams[1]
+            s.wait_event(self.stats_done[k])
+        with torch.cuda.stream(s):
+            s.wait_event(self.hist_done[(k - 1) % self.depth])  # report i-1's history update first
+            if self.rep.exchange:
+                self.part_g[k].replay()
+                self.hist_done[k].record(s)
+                # the eager all_gather of this slot's partials, ordered after them on s (every
+                # rank submits its reports, hence its collectives, in the same order)
+                self.rep._exchange(self.slots[k])
+                self.fin_g[k].replay()
+            else:
+                self.rest_g[k].replay()
+                self.hist_done[k].record(s)
+        self.done[k].record(s)
+
+    def _submit_whole(self, k: int, timed: bool) -> None:
+        if timed:
+            self.ev[0].record()
+            self.stats.replay()
+            self.ev[1].record()
+            self.rest[k].replay()
+        else:
+            self.full[k].replay()
+        self.done[k].record()
 
     def _land(self):
         k, timed = self.pending.pop(0)  # timed: the timed statistics phases (0: untimed)
@@ -774,7 +766,7 @@ class PipelinedReports:
                                "while the report was in flight (submit() -> collect()); its "
                                "results are undefined -- modify inputs only after collect()")
         ms = self.ev[0].elapsed_time(self.ev[1]) / timed if timed else None
-        return self.rep._unpack(self.bufs[k]), ms
+        return self.slots[k].unpack(self.bufs[k]), ms
 
     def collect(self):
         """(BatchResult, statistics ms for a timed report or None) of the oldest report, once it

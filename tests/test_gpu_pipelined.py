@@ -176,10 +176,7 @@ def test_two_in_flight_on_two_streams_keep_history_order(records, mode):
         b = batch.MatrixReporter(R, K, cap=256, thr_rel=0.8, thr_ind=0.8)
         run = lambda x: a.report_records(x, off)  # noqa: E731
         buf = torch.empty_like(src[0])
-        # (pipelined_records has no depth argument: PipelinedReports directly, as it builds it)
-        pipe = batch.PipelinedReports(b, None, 0, timing=True, mode=mode, depth=depth,
-                                      stats_bytes=8 * buf.shape[0],
-                                      stats=lambda: b.compute_stats_records(buf, off))
+        pipe = b.pipelined_records(buf, off, timing=True, mode=mode, depth=depth)
     else:
         S = 700
         src = [synth.synth_matrix(R, K, S, seed=40 + i, device="cuda") for i in range(2)]
@@ -283,6 +280,51 @@ def test_eager_work_while_reports_in_flight_is_ordered(records):
     got += [pipe.collect()[0], e7]
     assert len(got) == len(want)
     for w, x in zip(want, got):
+        _same(w, x)
+
+
+@pytest.mark.parametrize("records", [False, True])
+def test_own_buffers_are_never_rebound(records):
+    """Every report in flight has its own buffer set and the reporter's own is set 0: a pipeline
+    three deep never rebinds the reporter's statistics or history (nor reallocates the own set's
+    bucketing scratch per report), and an eager report issued while two reports are in flight
+    gives, bit for bit, a fresh reporter's at the same point of the sequence."""
+    R, K, S, cap = 8, 64, 200, 128
+    mk = lambda: batch.MatrixReporter(R, K, cap=cap, thr_rel=0.8, thr_ind=0.8)  # noqa: E731
+    rep, fresh = mk(), mk()
+    ptrs = lambda: (rep.stats.num.data_ptr(), rep.stats.med.data_ptr(), rep.hist.data_ptr())  # noqa: E731
+    own = ptrs()
+    if records:
+        counts = synth.zipf_counts(K, top=600)
+        slot, occ = synth.zipf_order(counts)
+        t = lambda a: torch.from_numpy(a.view(np.int32)).cuda()  # noqa: E731
+        src = [synth.synth_records(R, t(slot), t(occ), K, int(counts.max()), seed=90 + i) for i in range(2)]
+        off = torch.arange(R + 1, dtype=torch.int64, device="cuda") * slot.size
+        run = lambda r, x: r.report_records(x, off)  # noqa: E731
+        pipe = rep.pipelined_records(src[0], off, mode="alt", depth=3)
+        scratch = [a.data_ptr() for a in rep.own.bucket[:3]]  # allocated once, by the warm-up
+    else:
+        src = [synth.synth_matrix(R, K, S, seed=90 + i, device="cuda") for i in range(2)]
+        run = lambda r, x: r.report(x, S)  # noqa: E731
+        pipe = rep.pipelined(src[0], S, mode="alt", depth=3)
+    assert pipe.depth == 3 and pipe.slots[0] is rep.own
+    want = [run(fresh, src[i]) for i in (0, 0, 0, 0, 0, 1, 0)]
+    for _ in range(3):
+        pipe.submit()
+    assert ptrs() == own              # three in flight
+    got = [pipe.collect()[0] for _ in range(3)]
+    assert ptrs() == own
+    pipe.submit()
+    pipe.submit()
+    eager = run(rep, src[1])          # queues behind the two in flight
+    got += [pipe.collect()[0], pipe.collect()[0], eager]
+    pipe.submit()
+    got.append(pipe.collect()[0])
+    assert ptrs() == own
+    if records:
+        assert [a.data_ptr() for a in rep.own.bucket[:3]] == scratch
+    for w, x in zip(want, got):
+        assert x.err == w.err
         _same(w, x)
 
 
