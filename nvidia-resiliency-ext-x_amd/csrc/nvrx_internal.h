@@ -8,7 +8,7 @@
 namespace nvrx {
 
 // longest retained segment the one-workgroup EXACT kernel sorts in LDS (128 KiB of f32); longer
-// rings (up to NVRX_MAX_SEGMENT) sort in device scratch (exact_global_body, segment_kernels.h)
+// rings (up to NVRX_MAX_SEGMENT) sort in device scratch (exact_global_body, segment_sorted.h)
 #define NVRX_LDS_SEGMENT 32768
 
 hipError_t segment_stats_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
@@ -50,7 +50,7 @@ hipError_t section_stats(const double* vals, const int64_t* off, int64_t nsec, i
 hipError_t stragglers(const double* score, int64_t n, double thr, uint8_t* mask, hipStream_t st);
 
 #define NVRX_RECORDS_MAX_LDS (144 * 1024)
-// Stream-ordered device scratch from a private memory pool per device (segment_ragged.hip): it keeps
+// Stream-ordered device scratch from a private memory pool per device (scratch.cpp): it keeps
 // up to NVRX_SCRATCH_KEEP_BYTES of freed blocks across synchronisations, so steady-state reports
 // do not return to the driver, while a long-ring report's larger scratch goes back to the job.
 #define NVRX_SCRATCH_KEEP_BYTES ((uint64_t)256 << 20)

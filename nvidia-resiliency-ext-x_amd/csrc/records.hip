@@ -24,7 +24,7 @@
 
 #include <algorithm>
 
-#include "segment_kernels.h"
+#include "segment_sorted.h"
 
 namespace nvrx {
 
@@ -366,7 +366,7 @@ void records_bucket_kernel(
                     const u32x4 a = sv[st / 4];
                     const u32x4 b = keep > 4 ? sv[st / 4 + 1] : u32x4{~0u, ~0u, ~0u, ~0u};
                     unsigned v[RB_TINY] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-                    lane_stats<RB_TINY>(v, (int)keep, t * seg_stride + slot_lo + s, tiny, ColRef{});
+                    lane_stats<RB_TINY>(v, (int)keep, t * seg_stride + slot_lo + s, tiny, ColRef::none());
                 }
             }
         }

@@ -1,0 +1,78 @@
+// segment_addr.h -- where a segment lies in memory (strided, ragged), the fused column
+// reference and the empty result: what every statistics kernel takes as arguments.
+#pragma once
+#include "nvrx_common.h"
+#include "nvrx_internal.h"
+
+namespace nvrx {
+
+struct StridedSegs {  // segment s = base[s*stride + begin : + len], last `cap` kept
+    const uint32_t* base;
+    int64_t stride, begin, len, cap;
+    __device__ __forceinline__ void get(int64_t s, const uint32_t*& p, int& n) const {
+        int64_t keep = (cap > 0 && len > cap) ? cap : len;
+        p = base + s * stride + begin + (len - keep);
+        n = (int)keep;
+    }
+};
+struct RaggedSegs {  // segment s = base[off[s] : off[s] + len[s]] (len NULL: off[s+1]), last `cap` kept;
+                     // len[s] < 0: skipped (already reduced, e.g. by records_stats)
+    const uint32_t* base;
+    const int64_t* off;
+    const int32_t* lens;
+    int64_t cap;
+    __device__ __forceinline__ void get(int64_t s, const uint32_t*& p, int& n) const {
+        const int64_t b = off[s];
+        const int64_t e = lens ? b + lens[s] : off[s + 1];
+        const int64_t len = e - b;
+        int64_t keep = (cap > 0 && len > cap) ? cap : len;
+        p = base + (e - keep);
+        n = (int)keep;
+    }
+    // the retained length alone (no offset load when `lens` is given)
+    __device__ __forceinline__ int kept_len(int64_t s) const {
+        const int64_t len = lens ? (int64_t)lens[s] : off[s + 1] - off[s];
+        return (int)((cap > 0 && len > cap) ? cap : len);
+    }
+};
+
+// Optional fused per-column reference (segment s = row s / ncols, column s % ncols):
+// minbits[c] = atomicMin of the float bits of MED (non-negative floats order like their
+// bit patterns), missing[c] |= 1 for an empty segment -- _all_reduce_times'
+// MIN-over-ranks with the -1 => NaN rule (reporting.py:255-296), done in the epilogue.
+struct ColRef {
+    uint32_t* minbits;
+    uint32_t* missing;
+    int64_t ncols;
+    double inv;  // 1.0 / ncols
+    // no column reference: add / miss do nothing
+    static constexpr __host__ __device__ ColRef none() { return ColRef{nullptr, nullptr, 1, 1.0}; }
+    // s % ncols without a 64-bit integer divide: the f64 quotient is off by at most one
+    // for s < 2^52
+    __device__ __forceinline__ int64_t col(int64_t s) const {
+        int64_t q = (int64_t)((double)s * inv);
+        int64_t r = s - q * ncols;
+        if (r < 0) r += ncols;
+        if (r >= ncols) r -= ncols;
+        return r;
+    }
+    __device__ __forceinline__ void add(int64_t s, float med) const {
+        if (minbits) atomicMin(&minbits[col(s)], __float_as_uint(med));
+    }
+    __device__ __forceinline__ void miss(int64_t s) const {
+        if (minbits) atomicOr(&missing[col(s)], 1u);
+    }
+};
+
+__device__ __forceinline__ void write_empty(const nvrx_stats_soa& o, int64_t s) {
+    // KernelStats() default: num_calls 0, every float NaN (CuptiProfiler.h:39-45)
+    const float q = __builtin_nanf("");
+    o.num[s] = 0;
+    o.min[s] = q;
+    o.max[s] = q;
+    o.med[s] = q;
+    o.avg[s] = q;
+    o.std[s] = q;
+}
+
+}  // namespace nvrx

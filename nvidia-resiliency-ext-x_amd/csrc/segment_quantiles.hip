@@ -10,7 +10,7 @@
 // (the permilles travel by value in the kernel arguments); out is quantile-major [nq][nseg].
 //
 // Register path (retained length + misalignment <= 8192), one wave per segment: the samples
-// are loaded once with load_segment (segment_kernels.h: the PL ladder, 16-byte buffer loads) and
+// are loaded once with load_segment (segment_wave.h: the PL ladder, 16-byte buffer loads) and
 // selected MSB-first on d = x - MIN with a wave-private LDS histogram of Bins<PL>::NB bins.  The
 // state of rank q (its window [lo, lo + 2^sh), the count below it, the count inside it) lives in
 // lane q; ranks whose windows coincide form a group that is resolved once:
@@ -29,7 +29,7 @@
 // NaN and num 0 (as nvrx_segment_stats_ragged).  Segments of a few samples still take a whole wave
 // (a lane-per-segment class is not built).
 
-#include "segment_kernels.h"
+#include "segment_wave.h"
 
 namespace nvrx {
 namespace {

@@ -11,8 +11,8 @@
 //   n <= 8..128       one LANE per segment: the samples in registers, a sorting
 //                     sorting network, then CuptiProfiler.cpp:53-71 statement by
 //                     statement (sequential f32 sums) -- every field bit-exact
-//   n <= 64*PL        one WAVE per segment (lean_core, segment_kernels.h), PL 4..128
-//   longer / EXACT    one WORKGROUP per segment (exact_body)
+//   n <= 64*PL        one WAVE per segment (lean_core, segment_wave.h), PL 4..128
+//   longer / EXACT    one WORKGROUP per segment (exact_body, segment_sorted.h)
 //
 // Classification is three small launches over the segment lengths (count per block,
 // scan, scatter) into one id list ordered by class; every class kernel is persistent
@@ -23,36 +23,156 @@
 #include "segment_ragged_kernels.h"
 
 namespace nvrx {
+namespace ragged {
 
-// (nvrx_internal.h) scratch comes from a memory pool of the library's own per device,
-// whose release threshold is capped: freed scratch up to NVRX_SCRATCH_KEEP_BYTES stays reserved for
-// the next report; above it (the long-ring paths: up to 4 B per retained sample of the segments in
-// flight) it is released at the next synchronisation instead of staying taken from the training job.
-// The device's default pool -- PyTorch's hipMallocAsync allocator backend sets its threshold to keep
-// everything -- is left as the job configured it.  Inside a stream capture the allocation is the
-// graph's own node (hipMallocAsync: the graph memory pool).
-hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipError_t e = hipStreamIsCapturing(st, &cs); e != hipSuccess) return e;
-    if (cs != hipStreamCaptureStatusNone) return hipMallocAsync(p, bytes, st);
-    static std::once_flag once[64];
-    static hipMemPool_t pools[64] = {};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipMallocAsync(p, bytes, st);
-    std::call_once(once[dev], [dev] {
-        hipMemPoolProps props{};
-        props.allocType = hipMemAllocationTypePinned;
-        props.location.type = hipMemLocationTypeDevice;
-        props.location.id = dev;
-        hipMemPool_t pool = nullptr;
-        if (hipMemPoolCreate(&pool, &props) != hipSuccess) return;  // the default pool then
-        uint64_t thr = NVRX_SCRATCH_KEEP_BYTES;
-        (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &thr);
-        pools[dev] = pool;
-    });
-    return pools[dev] ? hipMallocFromPoolAsync(p, bytes, pools[dev], st) : hipMallocAsync(p, bytes, st);
+// ---------------------------------------------------------------- the classifier
+// Wave-aggregated class counting: one LDS atomic per distinct class present in the
+// wave (leader = lowest lane); returns this lane's rank among same-class lanes plus the
+// class's previous count.  cls < 0: lane does not take part.
+__device__ __forceinline__ uint32_t wave_class_add(uint32_t* lcnt, int cls) {
+    uint64_t pending = __ballot(cls >= 0);
+    uint32_t mine = 0;
+    while (pending) {
+        const int leader = __builtin_ffsll(pending) - 1;
+        const int c = __builtin_amdgcn_readlane(cls, leader);
+        const uint64_t grp = __ballot(cls == c) & pending;
+        uint32_t base = 0;
+        if (lane_id() == leader) base = atomicAdd(&lcnt[c], (uint32_t)__popcll(grp));
+        base = __builtin_amdgcn_readlane(base, leader);
+        if (cls == c) mine = base + mbcnt(grp);
+        pending &= ~grp;
+    }
+    return mine;
 }
+
+constexpr int CLS_THREADS = 1024;
+constexpr int CLS_MAX_BLOCKS = 1024;
+// segment lengths loaded per thread before any is classified: a block's chunk is tens of
+// thousands of segments, and one dependent load per 1024 of them left both passes
+// latency-bound (configs[3]: 153 + 118 us for 33.5 M segments)
+constexpr int CLS_BATCH = 8;
+static_assert(CLS_BATCH >= 1 && CLS_BATCH < 16 && 4 * NCLASS <= 64, "4-bit packed class counts per batch");
+
+// pass 1: per-block class counts (bcnt[b][c]); empty segments are written here
+__global__ __launch_bounds__(CLS_THREADS) void classify_count_kernel(
+    RaggedSegs segs, int64_t nseg, int64_t chunk, int aligned16, int exact, int full_n, uint32_t* bcnt,
+    nvrx_stats_soa out) {
+    const ColRef cr = ColRef::none();  // column references: kernel_ref afterwards
+    __shared__ uint32_t lcnt[NCLASS];
+    if (threadIdx.x < NCLASS) lcnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(nseg, lo + chunk);
+    // per-lane class counters in registers (no LDS traffic per segment), one wave reduction
+    // and one LDS add per class at the end
+    unsigned mine[NCLASS];
+#pragma unroll
+    for (int c = 0; c < NCLASS; ++c) mine[c] = 0u;
+    for (int64_t b = lo; b < hi; b += CLS_THREADS * CLS_BATCH) {
+        int n[CLS_BATCH];
+#pragma unroll
+        for (int j = 0; j < CLS_BATCH; ++j) {
+            const int64_t s = b + j * CLS_THREADS + threadIdx.x;
+            n[j] = s < hi ? segs.kept_len(s) : -1;
+        }
+        // the batch's class counts packed 4 bits per class in one 64-bit word (one shift and
+        // add per segment instead of a compare and add per class), unpacked once per batch
+        uint64_t pk = 0;
+#pragma unroll
+        for (int j = 0; j < CLS_BATCH; ++j) {
+            const int64_t s = b + j * CLS_THREADS + threadIdx.x;
+            if (n[j] == 0) {
+                write_empty(out, s);
+                cr.miss(s);
+            } else if (n[j] > 0) {  // n < 0: reduced elsewhere (or past the chunk)
+                pk += 1ull << (4 * seg_class(n[j], aligned16 != 0, exact != 0, full_n));
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NCLASS; ++c) mine[c] += (uint32_t)(pk >> (4 * c)) & 15u;
+    }
+#pragma unroll
+    for (int c = 0; c < NCLASS; ++c) {
+        const unsigned w = wave_sum_u32(mine[c]);
+        if (lane_id() == 0 && w) atomicAdd(&lcnt[c], w);
+    }
+    __syncthreads();
+    if (threadIdx.x < NCLASS) bcnt[(int64_t)blockIdx.x * NCLASS + threadIdx.x] = lcnt[threadIdx.x];
+}
+
+// pass 2 (one block): boff[b][c] = start of class c + blocks before b; cls[c] = {start, count}
+__global__ __launch_bounds__(CLS_MAX_BLOCKS) void classify_scan_kernel(uint32_t* bcnt, int nblocks,
+                                                                       uint32_t* cls) {
+    __shared__ uint32_t wsum[CLS_MAX_BLOCKS / 64];
+    const int b = threadIdx.x;
+    const int w = b >> 6;
+    uint32_t start = 0;
+    for (int c = 0; c < NCLASS; ++c) {
+        const uint32_t v = b < nblocks ? bcnt[(int64_t)b * NCLASS + c] : 0u;
+        const uint32_t incl = wave_incl_scan_u32(v);
+        if (lane_id() == 63) wsum[w] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (int j = 0; j < CLS_MAX_BLOCKS / 64; ++j) {
+            before += j < w ? wsum[j] : 0u;
+            all += wsum[j];
+        }
+        if (b < nblocks) bcnt[(int64_t)b * NCLASS + c] = start + before + incl - v;
+        if (b == 0) {
+            cls[2 * c] = start;
+            cls[2 * c + 1] = all;
+        }
+        start += all;
+        __syncthreads();
+    }
+}
+
+// pass 3: scatter segment ids into the class-ordered list
+__global__ __launch_bounds__(CLS_THREADS) void classify_scatter_kernel(
+    RaggedSegs segs, int64_t nseg, int64_t chunk, int aligned16, int exact, int full_n, const uint32_t* boff,
+    uint32_t* list) {
+    __shared__ uint32_t lcnt[NCLASS];
+    __shared__ uint32_t lbase[NCLASS];
+    if (threadIdx.x < NCLASS) {
+        lcnt[threadIdx.x] = 0u;
+        lbase[threadIdx.x] = boff[(int64_t)blockIdx.x * NCLASS + threadIdx.x];
+    }
+    __syncthreads();
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = min(nseg, lo + chunk);
+    for (int64_t b = lo; b < hi; b += CLS_THREADS * CLS_BATCH) {
+        int n[CLS_BATCH];
+#pragma unroll
+        for (int j = 0; j < CLS_BATCH; ++j) {
+            const int64_t s = b + j * CLS_THREADS + threadIdx.x;
+            n[j] = s < hi ? segs.kept_len(s) : -1;
+        }
+#pragma unroll
+        for (int j = 0; j < CLS_BATCH; ++j) {  // the same order as the counting pass
+            const int64_t s = b + j * CLS_THREADS + threadIdx.x;
+            const int cls = n[j] > 0 ? seg_class(n[j], aligned16 != 0, exact != 0, full_n) : -1;
+            const uint32_t r = wave_class_add(lcnt, cls);
+            if (cls >= 0) list[lbase[cls] + r] = (uint32_t)s;
+        }
+    }
+}
+
+// CUs of the current device (the class kernels' grids), asked once per device
+int cu_count() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (cus[dev] == 0) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            n <= 0)
+            n = 256;
+        cus[dev] = n;
+    }
+    return cus[dev];
+}
+
+}  // namespace ragged
 
 using namespace ragged;
 
@@ -123,9 +243,11 @@ static hipError_t ragged_join(hipStream_t st, Fork* f) {
     return hipSuccess;
 }
 
-hipError_t ragged_launch_classes(const RaggedSegs& segs, const uint32_t* cls_list, const uint32_t* cls,
-                                 int64_t keep, bool aligned16, bool exact, const nvrx_stats_soa& out,
-                                 hipStream_t st) {
+// The class kernels over the class-ordered segment list: keep = the longest retained segment;
+// classes it rules out are not launched.
+static hipError_t ragged_launch_classes(const RaggedSegs& segs, const uint32_t* cls_list,
+                                        const uint32_t* cls, int64_t keep, bool aligned16, bool exact,
+                                        const nvrx_stats_soa& out, hipStream_t st) {
     const uint32_t* list = cls_list;
     const int64_t need = aligned16 ? keep : keep + 3;
     // class kernels; classes that max_len rules out are not launched.  With side streams the

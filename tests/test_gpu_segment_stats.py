@@ -351,7 +351,7 @@ def test_grouped_full_segments(n, mult):
     rng = np.random.default_rng(n)
     K = 37
     nseg = K * mult
-    group = min(8, max(1, nseg // 32768))  # segment_kernels.h lean_group
+    group = min(8, max(1, nseg // 32768))  # segment_stats.hip lean_group
     assert group > 1 and nseg % group  # groups of 4 or 8 and a partial last group
     host = rng.integers(2000, 2_200_000, size=nseg * n, dtype=np.uint32)
     edges = _edge_segments(n)
@@ -377,6 +377,40 @@ def test_grouped_full_segments(n, mult):
     want = O.kernel_ref(ref["num"].reshape(-1, K), ref["med"].reshape(-1, K))
     got = col.cpu().numpy()
     assert np.array_equal(got[:K].view(np.float32), want) and not got[K:].any()
+
+
+@pytest.mark.parametrize("L,W", [(200, 8), (400, 7)])  # segment_ragged_kernels.h LIST4_OCC, LIST8_OCC
+def test_list_chunk_epilogue(L, W):
+    """The wave classes of PL 4 / 8 (seg_stats_list_kernel) keep a chunk's results one per lane
+    and emit them once per chunk.  A chunk is CH = max(1, min(16, cnt / (4 G))) list entries,
+    G = 4 * CUs * W waves: cnt = 2 * 4 * G + 5 is the fewest segments with CH = 2 -- a result in
+    lane 1 -- and leaves a partial last chunk.  List order inside a class is not fixed, so the
+    edge distributions (wide keys, clusters, zeros) go to 64 random segments: both lanes of a
+    chunk get them."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    G = 4 * cus * W
+    cnt = 2 * 4 * G + 5
+    assert min(16, cnt // (4 * G)) == 2 and cnt % 2
+    rng = np.random.default_rng(L)
+    host = rng.integers(2000, 2_200_000, size=cnt * L, dtype=np.uint32)
+    edges = _edge_segments(L)
+    where = rng.choice(cnt, 64, replace=False)
+    for i, w in enumerate(where):
+        host[w * L:(w + 1) * L] = edges[i % len(edges)]
+    off = np.arange(cnt + 1, dtype=np.int64) * L  # every segment 16-B aligned
+    ns = torch.from_numpy(host.view(np.int32)).to(DEV)
+    st = ops.segment_stats_ragged(ns, torch.from_numpy(off).to(DEV), None, max_len=L, cap=0,
+                                  mode=ops.STATS_FAST, aligned16=True)
+    ref = _oracle_segments(host, cnt, L, 0, L, 0)
+    _check(st, ref)
+    g = st.cpu()
+    x = host.reshape(cnt, L).astype(np.float64)
+    avg, std = x.mean(axis=1) / 1000.0, x.std(axis=1) / 1000.0
+    for w in where:
+        v = key_values(host[w * L:(w + 1) * L])
+        avg[w], std[w] = v.mean() / 1000.0, v.std() / 1000.0
+    np.testing.assert_allclose(g.avg.numpy(), avg, rtol=2.5e-7, atol=1e-30)
+    np.testing.assert_allclose(g.std.numpy(), std, rtol=1e-6, atol=1e-6 * avg.max())
 
 
 @pytest.mark.parametrize("keep,nfull", [(1024, 4 * 8300 + 3), (2048, 4 * 40 + 1), (4096, 4 * 25 + 2),
