@@ -28,6 +28,7 @@
  *   nvrx_profiler_*        nvrx_cupti_module.CuptiProfiler (ctor, initialize, shutdown,
  *                          start, stop, get_stats, reset)                                 cupti_src/cupti_module_py.cpp:33-54
  *   nvrx_records_*         CuptiProfiler::bufferCompleted record loop + CircularBuffer     cupti_src/CuptiProfiler.cpp:168-203, CircularBuffer.h:53-69
+ * Beyond the reference (no counterpart there): nvrx_segment_quantiles_*, nvrx_score_attribution.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -216,6 +217,57 @@ int nvrx_section_scores(const double* med, const uint8_t* present, int64_t R, in
                         double* hist, int32_t round_f32, double* out_rel, double* out_ind,
                         int32_t* err, void* stream);
 int nvrx_stragglers(const double* score, int64_t n, double thr, uint8_t* mask, void* stream);
+
+/* Score attribution: the kernels behind a rank's GPU score.  No reference counterpart (the
+ * reference reports the score alone).  The score of a row is sum_k s_k*w_k / sum_k w_k with
+ * s_k = base_k / MED_k and w_k = NUM_k * AVG_k (base: the relative reference or the individual
+ * history), so
+ *     1 - score = sum_k w_k * (1 - s_k) / sum_k w_k
+ * and loss_k = w_k * (1 - s_k) is the time (us, weighted as the score weights it) the rank lost
+ * on kernel k against its base.  Per row the call returns the `top` largest losses.
+ * Inputs: the fields of nvrx_score_args with the same meaning; `kind` selects the base
+ * (NVRX_ATTR_RELATIVE: ref / ref_index / ref_missing; NVRX_ATTR_INDIVIDUAL: hist / hist_index /
+ * hist_stride).  The history is READ ONLY here: it is taken as the report's nvrx_scores left it
+ * (already min(hist, MED)).  An element is eligible exactly when nvrx_scores adds it to the sum
+ * of that kind (col_valid NULL or nonzero, num > 0; relative: ref >= 0 and not missing).  An
+ * eligible element with MED == 0 sets *err |= 1 and is left out; one whose loss is NaN (a NaN
+ * AVG, say) is left out like an absent kernel; what is left out adds nothing to wsum either.
+ * Per element, in f64 with separately rounded operations:
+ *     m = MED;  w = NUM * AVG;  s = base / m;  loss = w * (1.0 - s)
+ * Outputs, row-major, j < top (1 <= top <= NVRX_MAX_ATTRIBUTION):
+ *     idx[r][j]    column of the j-th largest loss (ties: the lower column first; -0.0 == +0.0),
+ *                  -1 beyond the number of elements taken
+ *     loss[r][j]   its loss (negative when a caller's reference exceeds MED); NaN where idx = -1
+ *     score[r][j]  its s; NaN where idx = -1
+ *     wsum[r]      sum of w over the elements taken, in a fixed order (run-to-run identical);
+ *                  may be NULL, as may err
+ * K < 2^31.  R == 0 or K == 0 launches nothing (the outputs are untouched).  Stream-ordered: kernels on `stream` only, no allocation, no
+ * synchronisation (capturable in a graph). */
+#define NVRX_MAX_ATTRIBUTION 16
+#define NVRX_ATTR_RELATIVE 0
+#define NVRX_ATTR_INDIVIDUAL 1
+typedef struct nvrx_attribution_args {
+    int64_t R, K;
+    int32_t value_f64;
+    const int32_t* num;
+    const void* med;
+    const void* avg;
+    const uint8_t* col_valid;
+    const float* ref;
+    const int32_t* ref_index;
+    const uint32_t* ref_missing;
+    const void* hist;
+    const int32_t* hist_index;
+    int64_t hist_stride;
+    int32_t kind, top;
+    int32_t* idx;   /* [R][top] */
+    double* loss;   /* [R][top] */
+    double* score;  /* [R][top] */
+    double* wsum;   /* [R] or NULL */
+    int32_t* err;   /* [1] or NULL */
+} nvrx_attribution_args;
+int nvrx_score_attribution(const nvrx_attribution_args* args, void* stream);
+
 /* Statistics of section CPU timings (ms, float64): section s = vals[off[s] : off[s+1]]
  * (off: [nsec+1], device).  MIN, MAX, MED = lower median s[(n-1)/2] (torch.median),
  * AVG, STD = unbiased (NaN for n == 1), NUM -- Detector._get_section_summaries

@@ -4,7 +4,7 @@
 // status code + thread-local message, and the profiler handle that replaces the
 // reference's nvrx_cupti_module.CuptiProfiler (straggler/cupti_src/CuptiProfiler.cpp,
 // cupti_module_py.cpp).  All arithmetic runs in the HIP kernels of segment_stats.hip,
-// scores.hip and records.hip.
+// scores.hip, attribution.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -211,6 +211,34 @@ int nvrx_scores(const nvrx_score_args* a, void* stream) {
     NVRX_CHECK_ARG(a->reset_ncols >= 0 && (a->reset_ncols == 0 || (a->reset_col_ref && a->done)),
                    "nvrx_scores: reset_col_ref needs done and reset_ncols >= 0");
     return hip_status(nvrx::scores(*a, S(stream)), "nvrx_scores");
+}
+
+int nvrx_score_attribution(const nvrx_attribution_args* a, void* stream) {
+    NVRX_CHECK_ARG(a, "nvrx_score_attribution: null args");
+    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
+                   "nvrx_score_attribution: top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    NVRX_CHECK_ARG(a->kind == NVRX_ATTR_RELATIVE || a->kind == NVRX_ATTR_INDIVIDUAL,
+                   "nvrx_score_attribution: unknown kind (NVRX_ATTR_RELATIVE or NVRX_ATTR_INDIVIDUAL)");
+    NVRX_CHECK_ARG(a->R >= 0, "nvrx_score_attribution: negative R");
+    NVRX_CHECK_ARG(a->K >= 0, "nvrx_score_attribution: negative K");
+    NVRX_CHECK_ARG(a->R < (int64_t)1 << 31, "nvrx_score_attribution: R must be below 2^31");
+    NVRX_CHECK_ARG(a->K < (int64_t)1 << 31, "nvrx_score_attribution: K must be below 2^31");
+    NVRX_CHECK_ARG(a->value_f64 == 0 || a->value_f64 == 1, "nvrx_score_attribution: bad value_f64");
+    NVRX_CHECK_ARG(!a->hist_index || a->hist_stride > 0,
+                   "nvrx_score_attribution: hist_index requires hist_stride");
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->num, "nvrx_score_attribution: null num");
+        NVRX_CHECK_ARG(a->med, "nvrx_score_attribution: null med");
+        NVRX_CHECK_ARG(a->avg, "nvrx_score_attribution: null avg");
+        NVRX_CHECK_ARG(a->idx, "nvrx_score_attribution: null idx");
+        NVRX_CHECK_ARG(a->loss, "nvrx_score_attribution: null loss");
+        NVRX_CHECK_ARG(a->score, "nvrx_score_attribution: null score");
+        NVRX_CHECK_ARG(a->kind != NVRX_ATTR_RELATIVE || a->ref,
+                       "nvrx_score_attribution: the relative kind needs ref");
+        NVRX_CHECK_ARG(a->kind != NVRX_ATTR_INDIVIDUAL || a->hist,
+                       "nvrx_score_attribution: the individual kind needs hist");
+    }
+    return hip_status(nvrx::score_attribution(*a, S(stream)), "nvrx_score_attribution");
 }
 
 int nvrx_finalize_scores(const double* partials, int64_t R, int64_t nshards, int32_t round_f32,

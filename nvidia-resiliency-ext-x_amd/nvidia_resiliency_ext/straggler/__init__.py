@@ -1,9 +1,11 @@
 """Straggler detection, MI355X-native (drop-in for nvidia_resiliency_ext.straggler).
 
 Exports the reference's public names (reference straggler/__init__.py:16-18) plus
-``StragglerReport`` (alias of ``Report``) and ``ReportGenerator``.
+``StragglerReport`` (alias of ``Report``), ``ReportGenerator`` and ``KernelAttribution`` (what
+``Detector.kernel_attribution`` returns).
 """
-from .reporting import Report, ReportGenerator, StragglerId, StragglerReport  # noqa: F401
+from .reporting import (KernelAttribution, Report, ReportGenerator, StragglerId,  # noqa: F401
+                        StragglerReport)
 from .statistics import Statistic  # noqa: F401
 from .straggler import CallableId, Detector  # noqa: F401
 from . import reporting  # noqa: F401

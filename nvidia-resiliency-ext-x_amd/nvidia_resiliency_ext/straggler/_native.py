@@ -28,6 +28,9 @@ NVRX_STATS_EXACT = 1
 NVRX_STATS_COLREF_READY = 0x10
 NVRX_MAX_SEGMENT = 1 << 30  # rings above 32,768 samples sort in device scratch
 NVRX_MAX_QUANTILES = 8  # quantiles (permilles) one nvrx_*_quantiles* call resolves
+NVRX_MAX_ATTRIBUTION = 16  # kernels per row one nvrx_score_attribution call returns
+NVRX_ATTR_RELATIVE = 0
+NVRX_ATTR_INDIVIDUAL = 1
 
 P = ctypes.c_void_p
 i32 = ctypes.c_int32
@@ -50,6 +53,17 @@ class ScoreArgs(ctypes.Structure):
         ("round_f32", i32), ("thr_rel", f64), ("thr_ind", f64),
         ("gpu_rel", P), ("gpu_ind", P), ("strag_rel", P), ("strag_ind", P),
         ("done", P), ("reset_col_ref", P), ("reset_ncols", i64),
+    ]
+
+
+class AttributionArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("value_f64", i32),
+        ("num", P), ("med", P), ("avg", P), ("col_valid", P),
+        ("ref", P), ("ref_index", P), ("ref_missing", P),
+        ("hist", P), ("hist_index", P), ("hist_stride", i64),
+        ("kind", i32), ("top", i32),
+        ("idx", P), ("loss", P), ("score", P), ("wsum", P), ("err", P),
     ]
 
 
@@ -93,6 +107,7 @@ SIGNATURES = {
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),
+    "nvrx_score_attribution": (ctypes.c_int, [ctypes.POINTER(AttributionArgs), P]),
     "nvrx_finalize_scores": (ctypes.c_int, [P, i64, i64, i32, f64, f64, P, P, P, P, P, P]),
     "nvrx_section_scores": (ctypes.c_int, [P, P, i64, i64, P, P, P, P, i32, P, P, P, P]),
     "nvrx_stragglers": (ctypes.c_int, [P, i64, f64, P, P]),

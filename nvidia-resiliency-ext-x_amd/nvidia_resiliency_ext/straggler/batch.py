@@ -106,6 +106,17 @@ class BatchResult:
     err: int = 0
 
 
+@dataclass
+class BatchAttribution:
+    """MatrixReporter.attribute: per rank the `top` kernels that cost it most of its score."""
+    kernel: np.ndarray    # [R, top] i32 kernel column, largest loss first (-1: no further kernel)
+    loss_us: np.ndarray   # [R, top] f64 NUM*AVG * (1 - base/MED), NaN where kernel is -1
+    score: np.ndarray     # [R, top] f64 base/MED of that kernel
+    share: np.ndarray     # [R, top] f64 loss_us / wsum: the kernel's part of 1 - score
+    wsum: np.ndarray      # [R] f64 total weight of the rank's scored kernels
+    err: int = 0          # 1: some scored MED was 0 (that kernel is left out)
+
+
 @dataclass(eq=False)
 class _ReportBuffers:
     """The device buffers of one report: segment statistics, the per-kernel reference the
@@ -209,6 +220,8 @@ class MatrixReporter:
         self.hist = torch.full((R, K), float("inf"), dtype=torch.float32, device=d) if individual else None
         self.h_out = torch.empty(_ReportBuffers.nbytes(R), dtype=torch.uint8, pin_memory=True)
         self._pipes = weakref.WeakSet()  # PipelinedReports over this reporter
+        self._attr_ref = None  # attribute(): its own column reference and packed outputs per top
+        self._attr_out = {}
 
     @property
     def stats(self) -> ops.SegmentStats:
@@ -359,6 +372,52 @@ class MatrixReporter:
         self.compute_stats(ns, s_push)
         self.compute_scores()
         return self.land()
+
+    def attribute(self, top: int = 8, kind: str = "relative") -> BatchAttribution:
+        """Which kernels made each rank's score what it is: per rank the `top` (1..16) kernels
+        with the largest loss ``NUM*AVG * (1 - base/MED)``, base being the per-kernel reference
+        (kind="relative") or the rank's own history (kind="individual"); the losses of all of a
+        rank's kernels sum to ``(1 - score) * wsum``.  It explains the statistics in the reporter's
+        own buffer set -- the last report(), report_records() or own-set graph replay -- and
+        changes none of the report's buffers.  Beyond the reference (it reports the score only)."""
+        top, _ = ops.attribution_request(top, kind)
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.attribute: attribution across kernel shards "
+                                      "(exchange=True) is not supported")
+        if not (self.relative if kind == "relative" else self.individual):
+            raise RuntimeError(f"MatrixReporter.attribute: the reporter was built without "
+                               f"{kind} scores")
+        self._order_after_inflight()
+        R, K, d = self.R, self.K, self.device
+        st = self.own.stats.view(R, K)
+        n = R * top
+        buf = self._attr_out.get(top)
+        if buf is None:  # packed: [loss f64 n][score f64 n][wsum f64 R][idx i32 n][err i32]
+            buf = self._attr_out[top] = torch.zeros(8 * (2 * n + R) + 4 * (n + 1),
+                                                    dtype=torch.uint8, device=d)
+        f64, i32 = buf[:8 * (2 * n + R)].view(torch.float64), buf[8 * (2 * n + R):].view(torch.int32)
+        out = ops.ScoreAttribution(i32[:n], f64[:n], f64[n:2 * n], f64[2 * n:])
+        err = i32[n:]
+        err.zero_()
+        ref = None
+        if kind == "relative":
+            # the report's scores epilogue has reset col_ref by now: the reference is recomputed
+            # into buffers of attribute's own, the same way for every R
+            if self._attr_ref is None:
+                self._attr_ref = (torch.empty(max(K, 1), dtype=torch.float32, device=d),
+                                  torch.empty(2 * max(K, 1), dtype=torch.int32, device=d))
+            ref = ops.kernel_ref(st.num, st.med, ref=self._attr_ref[0], scratch=self._attr_ref[1])
+        ops.score_attribution(st.num, st.med, st.avg, top=top, kind=kind, col_valid=self.col_valid,
+                              ref=ref, hist=self.hist if kind == "individual" else None, err=err,
+                              out=out)
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        h64 = host[:8 * (2 * n + R)].view(np.float64)
+        h32 = host[8 * (2 * n + R):].view(np.int32)
+        loss, wsum = h64[:n].reshape(R, top).copy(), h64[2 * n:].copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = loss / wsum[:, None]
+        return BatchAttribution(h32[:n].reshape(R, top).copy(), loss,
+                                h64[n:2 * n].reshape(R, top).copy(), share, wsum, int(h32[n]))
 
     def graph(self, ns: torch.Tensor, s_push: int) -> "ReportGraph":
         """The report's device work captured once as HIP graphs, replayed per report (the

@@ -234,6 +234,69 @@ def scores(num, med, avg, *, col_valid=None, ref=None, ref_index=None, ref_missi
     return partials
 
 
+ATTRIBUTION_KINDS = {"relative": N.NVRX_ATTR_RELATIVE, "individual": N.NVRX_ATTR_INDIVIDUAL}
+
+
+@dataclass
+class ScoreAttribution:
+    """Per row, the `top` kernels with the largest loss w*(1 - s) (device tensors):
+    idx [R, top] int32 column (-1: fewer kernels than top), loss / score [R, top] float64
+    (NaN where idx is -1), wsum [R] float64 total weight of the kernels taken."""
+
+    idx: torch.Tensor
+    loss: torch.Tensor
+    score: torch.Tensor
+    wsum: torch.Tensor
+
+
+def attribution_request(top, kind):
+    """(top, kind code) as the C ABI takes them: top an int in [1, NVRX_MAX_ATTRIBUTION], kind
+    "relative" or "individual"; ValueError if not."""
+    if isinstance(top, bool) or not isinstance(top, numbers.Integral) or \
+            not 1 <= top <= N.NVRX_MAX_ATTRIBUTION:
+        raise ValueError(f"top must be an int in [1, {N.NVRX_MAX_ATTRIBUTION}], got {top!r}")
+    if not isinstance(kind, str) or kind not in ATTRIBUTION_KINDS:
+        raise ValueError(f"kind must be one of {sorted(ATTRIBUTION_KINDS)}, got {kind!r}")
+    return int(top), ATTRIBUTION_KINDS[kind]
+
+
+def score_attribution(num, med, avg, *, top, kind, col_valid=None, ref=None, ref_index=None,
+                      ref_missing=None, hist=None, hist_index=None, hist_stride=0, err=None,
+                      out: Optional[ScoreAttribution] = None, stream=None) -> ScoreAttribution:
+    """The kernels behind a score (no reference counterpart).  Inputs as ``scores``; per row the
+    `top` (1..16) largest ``loss = NUM*AVG * (1 - base/MED)`` with base the relative reference
+    (kind="relative": ref / ref_index / ref_missing) or the individual history as the report's
+    ``scores`` call left it (kind="individual": hist / hist_index / hist_stride; read only).
+    ``1 - score == loss.sum() / wsum`` over all of a row's kernels.  err (int32 [1], optional) is
+    OR-ed with 1 when an eligible MED is 0 (that kernel is left out); out: preallocated outputs."""
+    top, kind_code = attribution_request(top, kind)
+    for name, t in (("num", num), ("med", med), ("avg", avg)):
+        N.require_device(t, name)
+    R, K = med.shape
+    if avg.dtype != med.dtype or (hist is not None and hist.dtype != med.dtype):
+        raise TypeError("med, avg and hist must share one float dtype")
+    if kind_code == N.NVRX_ATTR_RELATIVE and ref is None:
+        raise ValueError("kind='relative' needs ref")
+    if kind_code == N.NVRX_ATTR_INDIVIDUAL and hist is None:
+        raise ValueError("kind='individual' needs hist")
+    if out is None:
+        d = med.device
+        out = ScoreAttribution(torch.empty((R, top), dtype=torch.int32, device=d),
+                               torch.empty((R, top), dtype=torch.float64, device=d),
+                               torch.empty((R, top), dtype=torch.float64, device=d),
+                               torch.empty(R, dtype=torch.float64, device=d))
+    elif (out.idx.numel() != R * top or out.loss.numel() != R * top or
+          out.score.numel() != R * top or out.wsum.numel() != R):
+        raise ValueError("score_attribution: preallocated outputs do not match [R, top]")
+    a = N.AttributionArgs(R, K, int(med.dtype == torch.float64), num.data_ptr(), med.data_ptr(),
+                          avg.data_ptr(), N.ptr(col_valid), N.ptr(ref), N.ptr(ref_index),
+                          N.ptr(ref_missing), N.ptr(hist), N.ptr(hist_index), hist_stride,
+                          kind_code, top, out.idx.data_ptr(), out.loss.data_ptr(),
+                          out.score.data_ptr(), out.wsum.data_ptr(), N.ptr(err))
+    N.call("nvrx_score_attribution", ctypes.byref(a), _stream(stream))
+    return out
+
+
 def finalize_scores(partials: torch.Tensor, R: int, nshards: int = 1, round_f32: bool = False,
                     thr_rel: float = 0.75, thr_ind: float = 0.75, rel=True, ind=True, err=None,
                     out: Optional[dict] = None, stream=None):

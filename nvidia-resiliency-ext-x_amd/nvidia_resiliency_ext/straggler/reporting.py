@@ -89,6 +89,16 @@ class Report:
 StragglerReport = Report
 
 
+@dataclasses.dataclass(frozen=True)
+class KernelAttribution:
+    """One kernel behind a GPU score (ReportGenerator.kernel_attribution; beyond the reference)."""
+
+    name: str
+    score: float    # base / MED of this kernel: 1.0 = as fast as the reference / the own best
+    loss_us: float  # NUM*AVG * (1 - score): weighted time lost on it
+    share: float    # loss_us / total weight: its part of 1 - (GPU score)
+
+
 class _History:
     """Per-name running minimum of MED on the device (min_local_*_times, reporting.py:186-191)."""
 
@@ -141,6 +151,7 @@ class ReportGenerator:
         self._kcache = None  # (kernel names, their ids, their history slots) of the last report
         self.rank_to_node: Dict[int, str] = collections.defaultdict(lambda: '<unk>')
         self._device: Optional[torch.device] = None
+        self._last_scored = None  # the device tensors _score_local scored last (kernel_attribution)
 
     # reference attribute names, materialised from the device history on access
     @property
@@ -238,6 +249,8 @@ class ReportGenerator:
                     times = t.to(dev)
                 else:
                     dist_utils.all_reduce(times, op=torch.distributed.ReduceOp.MIN, group=self.group)
+        # kept for kernel_attribution (references only: no transfer, no launch)
+        self._last_scored = (knames, d_knum, d_kmed, d_kavg, times, d_kid, d_kslot)
         partials = ops.scores(d_knum.view(1, K), d_kmed.view(1, K), d_kavg.view(1, K),
                               ref=times if rel else None, ref_index=d_kid if rel else None,
                               hist=self._hist_k.values if ind else None,
@@ -264,6 +277,44 @@ class ReportGenerator:
         srel = dict(zip(snames, map(float, out[2:2 + S]))) if rel else {}
         sind = dict(zip(snames, map(float, out[2 + S:2 + 2 * S]))) if ind else {}
         return (gi if ind else float("nan")), sind, (gr if rel else float("nan")), srel
+
+    def kernel_attribution(self, top: int = 8, kind: str = "relative") -> List[KernelAttribution]:
+        """The kernels behind this rank's GPU score in the last report: at most `top` (1..16)
+        entries, largest loss first, over the kernels that report scored (the relative reference
+        after its all-reduce, or the individual history as that report left it).  The losses of
+        all scored kernels sum to ``(1 - score)`` times their total weight, so the ``share`` of the
+        entries adds up to at most ``1 - score``.  Beyond the reference; local to the rank (no
+        collective), and neither the history nor the next report changes."""
+        top, _ = ops.attribution_request(top, kind)
+        if self._last_scored is None:
+            raise RuntimeError("kernel_attribution: no report has been generated yet")
+        if not (self.is_computing_rel_scores if kind == "relative"
+                else self.is_computing_indiv_scores):
+            raise RuntimeError(f"kernel_attribution: {kind} scores are not computed "
+                               "(scores_to_compute)")
+        knames, d_knum, d_kmed, d_kavg, times, d_kid, d_kslot = self._last_scored
+        K = len(knames)
+        if K == 0:
+            return []
+        rel = kind == "relative"
+        hist = None if rel else self._hist_k.values
+        res = ops.score_attribution(d_knum.view(1, K), d_kmed.view(1, K), d_kavg.view(1, K),
+                                    top=top, kind=kind, ref=times if rel else None,
+                                    ref_index=d_kid if rel else None, hist=hist,
+                                    hist_index=None if rel else d_kslot,
+                                    hist_stride=0 if rel else hist.numel())
+        out = torch.cat([res.idx.view(-1).to(torch.float64), res.loss.view(-1),
+                         res.score.view(-1), res.wsum]).cpu().numpy()  # one device->host transfer
+        wsum = float(out[3 * top])
+        entries = []
+        for j in range(top):
+            k = int(out[j])
+            if k < 0:
+                break
+            loss = float(out[top + j])
+            entries.append(KernelAttribution(knames[k], float(out[2 * top + j]), loss,
+                                             loss / wsum if wsum != 0.0 else math.nan))
+        return entries
 
     # ------------------------------------------------------------------ gather (reporting.py:338-419)
     def _get_tensor_from_scores(self, gi, si, gr, sr):

@@ -166,6 +166,17 @@ class Detector:
         return {n: tuple(float(x) for x in q[:, i]) for i, n in enumerate(names)}
 
     @classmethod
+    def kernel_attribution(cls, top: int = 8, kind: str = "relative"):
+        """The kernels behind this rank's GPU score in the LAST report: a list of at most `top`
+        (1..16) ``KernelAttribution(name, score, loss_us, share)``, largest loss first, where
+        ``loss_us = NUM*AVG * (1 - score)`` and the shares of all scored kernels sum to
+        ``1 - (GPU score)``.  kind: "relative" (against the best rank) or "individual" (against
+        this rank's own best).  Call it AFTER ``generate_report``; RuntimeError before the first
+        one.  Beyond the reference: local to the rank, no collective, the report is unchanged."""
+        assert cls.initialized
+        return cls.reporter.kernel_attribution(top=top, kind=kind)
+
+    @classmethod
     def _reset_sections_elapseds(cls):
         for section in cls.custom_sections.values():
             section.cpu_elapsed_times.clear()
