@@ -28,7 +28,8 @@
  *   nvrx_profiler_*        nvrx_cupti_module.CuptiProfiler (ctor, initialize, shutdown,
  *                          start, stop, get_stats, reset)                                 cupti_src/cupti_module_py.cpp:33-54
  *   nvrx_records_*         CuptiProfiler::bufferCompleted record loop + CircularBuffer     cupti_src/CuptiProfiler.cpp:168-203, CircularBuffer.h:53-69
- * Beyond the reference (no counterpart there): nvrx_segment_quantiles_*, nvrx_score_attribution.
+ * Beyond the reference (no counterpart there): nvrx_segment_quantiles_*, nvrx_score_attribution,
+ * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -187,6 +188,37 @@ int nvrx_segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off,
                                   const int32_t* seg_len, int64_t nseg, int64_t max_len,
                                   int64_t cap, int32_t aligned16, const int32_t* permille,
                                   int32_t nq, float* out, int32_t* num, void* stream);
+
+/* Duration histograms of the same segments, with FIXED buckets: the same edges for every segment,
+ * rank and report, so counts add -- over ranks to a fleet-wide distribution, over reports to a
+ * whole run's -- and any quantile is known to within one bucket.  No reference counterpart.
+ * Log-linear over the u32 duration key x, 3 mantissa bits, every bucket at most 12.5 % wide:
+ *   bucket(x) = x                                  x < 8
+ *             = 8*(e-2) + ((x >> (e-3)) & 7)       otherwise, e = 31 - clz(x)   (3..31)
+ *   edge(b)   = b                                  b < 8     (lower edge, a key)
+ *             = (8 + b%8) << (b/8 - 1)             otherwise; edge(240) := 2^32
+ * bucket is monotone in the key (hence in the duration); edge(bucket(x)) <= x < edge(bucket(x)+1);
+ * edge(238) == NVRX_KEY_WIDE, so buckets 238 and 239 hold exactly the wide keys (3.76 s and more)
+ * and every bucket below holds plain ns; an edge in us is its key converted like every sample.
+ * The scheme is part of the ABI.  nvrx_histogram_bucket / _edge are host functions (pure);
+ * _edge takes 0..240 (2^32 for 240) and returns UINT64_MAX outside.
+ * counts: [nseg][NVRX_HIST_BINS] u32 device memory, segment-major (16-byte aligned); num: [nseg]
+ * retained lengths, or NULL.  accumulate == 0: all 240 bins of every segment taken are written
+ * (no memset needed); != 0: the counts are added to what is there (one owner per segment, no
+ * atomics on device memory).  An empty segment gives zero bins (nothing added) and num 0; in the
+ * ragged call seg_len[s] < 0 skips segment s (outputs untouched).  Segments as for the statistics
+ * calls, the last min(len, cap) samples retained.  Every segment is read exactly once.
+ * Stream-ordered: kernels on `stream` only, no allocation, no synchronisation (capturable). */
+#define NVRX_HIST_BINS 240
+uint32_t nvrx_histogram_bucket(uint32_t key);
+uint64_t nvrx_histogram_edge(int32_t bucket);
+int nvrx_segment_histogram_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
+                                   int64_t seg_begin, int64_t seg_len, int64_t cap,
+                                   int32_t accumulate, uint32_t* counts, int32_t* num, void* stream);
+int nvrx_segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off,
+                                  const int32_t* seg_len, int64_t nseg, int64_t max_len,
+                                  int64_t cap, int32_t aligned16, int32_t accumulate,
+                                  uint32_t* counts, int32_t* num, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.
@@ -383,6 +415,13 @@ int nvrx_profiler_kernel_name(nvrx_profiler* p, uint32_t slot, char* buf, int64_
 int nvrx_profiler_get_quantiles(nvrx_profiler* p, const int32_t* permille, int32_t nq,
                                 int64_t cap_out, int64_t* count, uint32_t* slots, int32_t* num,
                                 float* out);
+/* Flush, then the histogram (nvrx_segment_histogram_ragged) of every slot with >= 1 record, over
+ * the records its ring retains.  Synchronous.  *count = number of kernels; fills up to cap_out
+ * entries of slots (sorted by kernel name, like get_stats), num (retained records) and out
+ * ([cap_out][NVRX_HIST_BINS] host u32: bin b of entry i at out[i * 240 + b]).  The record log and
+ * get_stats' cached result are left as they are; the call's own kernels are not captured. */
+int nvrx_profiler_get_histograms(nvrx_profiler* p, int64_t cap_out, int64_t* count,
+                                 uint32_t* slots, int32_t* num, uint32_t* out);
 /* Flush, then copy the record log since the last reset ({slot, ns}, push order per slot;
  * after a compaction only the records the rings can still retain) into host `out`
  * (up to cap_out records; *count = log length).  Synchronous.  No reference counterpart:

@@ -4,7 +4,7 @@
 // status code + thread-local message, and the profiler handle that replaces the
 // reference's nvrx_cupti_module.CuptiProfiler (straggler/cupti_src/CuptiProfiler.cpp,
 // cupti_module_py.cpp).  All arithmetic runs in the HIP kernels of segment_stats.hip,
-// scores.hip, attribution.hip and records.hip.
+// scores.hip, attribution.hip, segment_histogram.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -175,6 +175,62 @@ int nvrx_segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off,
     return hip_status(nvrx::segment_quantiles_ragged(ns, seg_off, seg_len, nseg, max_len, cap,
                                                      aligned16 != 0, permille, nq, out, num, S(stream)),
                       "nvrx_segment_quantiles_ragged");
+}
+
+// ------------------------------------------------------------------ histograms
+uint32_t nvrx_histogram_bucket(uint32_t key) {
+    if (key < 8) return key;
+    const int e = 31 - __builtin_clz(key);
+    return (uint32_t)(8 * (e - 2)) + ((key >> (e - 3)) & 7u);
+}
+
+uint64_t nvrx_histogram_edge(int32_t bucket) {
+    if (bucket < 0 || bucket > NVRX_HIST_BINS) return UINT64_MAX;
+    if (bucket < 8) return (uint64_t)bucket;
+    return (uint64_t)(8 + bucket % 8) << (bucket / 8 - 1);
+}
+
+int nvrx_segment_histogram_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
+                                   int64_t seg_begin, int64_t seg_len, int64_t cap,
+                                   int32_t accumulate, uint32_t* counts, int32_t* num, void* stream) {
+    NVRX_CHECK_ARG(nseg >= 0, "nvrx_segment_histogram_strided: negative nseg");
+    NVRX_CHECK_ARG(seg_len >= 0, "nvrx_segment_histogram_strided: negative seg_len");
+    NVRX_CHECK_ARG(seg_begin >= 0, "nvrx_segment_histogram_strided: negative seg_begin");
+    NVRX_CHECK_ARG(seg_stride >= 0, "nvrx_segment_histogram_strided: negative seg_stride");
+    NVRX_CHECK_ARG(nseg < (int64_t)1 << 31, "nvrx_segment_histogram_strided: nseg must be below 2^31");
+    NVRX_CHECK_ARG(nseg == 0 || counts, "nvrx_segment_histogram_strided: null counts");
+    NVRX_CHECK_ARG(((uintptr_t)counts & 15) == 0, "nvrx_segment_histogram_strided: counts not 16-byte aligned");
+    NVRX_CHECK_ARG(nseg == 0 || seg_len == 0 || ns, "nvrx_segment_histogram_strided: null ns");
+    NVRX_CHECK_ARG(nseg <= 1 || seg_stride >= seg_begin + seg_len,
+                   "nvrx_segment_histogram_strided: segments overlap (seg_stride < seg_begin + seg_len)");
+    const int64_t keep = (cap > 0 && seg_len > cap) ? cap : seg_len;
+    NVRX_CHECK_ARG(keep <= NVRX_MAX_SEGMENT,
+                   "nvrx_segment_histogram_strided: retained seg_len longer than NVRX_MAX_SEGMENT (2^30)");
+    if (nseg == 0) return NVRX_OK;
+    return hip_status(nvrx::segment_histogram_strided(ns, nseg, seg_stride, seg_begin, seg_len, cap,
+                                                      accumulate != 0, counts, num, S(stream)),
+                      "nvrx_segment_histogram_strided");
+}
+
+int nvrx_segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off,
+                                  const int32_t* seg_len, int64_t nseg, int64_t max_len,
+                                  int64_t cap, int32_t aligned16, int32_t accumulate,
+                                  uint32_t* counts, int32_t* num, void* stream) {
+    NVRX_CHECK_ARG(nseg >= 0, "nvrx_segment_histogram_ragged: negative nseg");
+    NVRX_CHECK_ARG(max_len >= 0, "nvrx_segment_histogram_ragged: negative max_len");
+    NVRX_CHECK_ARG(nseg < (int64_t)1 << 31, "nvrx_segment_histogram_ragged: nseg must be below 2^31");
+    NVRX_CHECK_ARG(nseg == 0 || counts, "nvrx_segment_histogram_ragged: null counts");
+    NVRX_CHECK_ARG(((uintptr_t)counts & 15) == 0, "nvrx_segment_histogram_ragged: counts not 16-byte aligned");
+    NVRX_CHECK_ARG(nseg == 0 || seg_off, "nvrx_segment_histogram_ragged: null seg_off");
+    NVRX_CHECK_ARG(nseg == 0 || max_len == 0 || ns, "nvrx_segment_histogram_ragged: null ns");
+    const int64_t keep = (cap > 0 && max_len > cap) ? cap : max_len;
+    NVRX_CHECK_ARG(keep <= NVRX_MAX_SEGMENT,
+                   "nvrx_segment_histogram_ragged: retained max_len longer than NVRX_MAX_SEGMENT (2^30)");
+    if (nseg == 0) return NVRX_OK;
+    return hip_status(nvrx::segment_histogram_ragged(ns, seg_off, seg_len, nseg, max_len, cap,
+                                                     aligned16 != 0, accumulate != 0, counts, num,
+                                                     S(stream)),
+                      "nvrx_segment_histogram_ragged");
 }
 
 // ------------------------------------------------------------------ scoring
@@ -946,6 +1002,60 @@ int nvrx_profiler_get_quantiles(nvrx_profiler* p, const int32_t* permille, int32
         if (num) num[i] = hnum[order[i]];
         if (out)
             for (int32_t j = 0; j < nq; ++j) out[j * cap_out + i] = hq[j * nslots + order[i]];
+    }
+    return NVRX_OK;
+}
+
+int nvrx_profiler_get_histograms(nvrx_profiler* p, int64_t cap_out, int64_t* count,
+                                 uint32_t* slots, int32_t* num, uint32_t* out) {
+    NVRX_CHECK_ARG(p, "nvrx_profiler_get_histograms: null handle");
+    NVRX_CHECK_ARG(count, "nvrx_profiler_get_histograms: null count");
+    NVRX_CHECK_ARG(cap_out >= 0, "nvrx_profiler_get_histograms: negative cap_out");
+    CaptureSelf self(p);  // the call's own kernels are not captured
+    (void)nvrx::capture_flush();
+    std::lock_guard<std::mutex> lk(p->mu);
+    DeviceGuard g(p->cfg.device);
+    int rc = flush_locked(p);
+    if (rc) return rc;
+    *count = 0;
+    const int64_t nslots = (int64_t)p->names.size();
+    if (p->log_n == 0 || nslots == 0) return NVRX_OK;
+    // the work buffer of the bucketing followed by num [nslots] (256-B aligned) and the counts
+    // [nslots][240]: sized before bucket_log so that its own ensure_work keeps the allocation
+    const size_t row = align256((size_t)nslots * 4);
+    const size_t span = row + (size_t)nslots * NVRX_HIST_BINS * 4;
+    const size_t carve_bytes = carve(nullptr, nslots, nvrx::records_bucket_capacity(p->log_n, 1, nslots)).bytes;
+    rc = ensure_work(p, carve_bytes + span);
+    if (rc) return rc;
+    Work w;
+    rc = bucket_log(p, nslots, 0, w);
+    if (rc) return rc;
+    char* extra = (char*)p->d_work + carve_bytes;
+    const int64_t cap = p->cfg.stats_max_len_per_kernel;
+    hipError_t e = nvrx::segment_histogram_ragged(w.ns, w.seg_off, w.seg_len, nslots,
+                                                  std::min<int64_t>(cap, p->log_n), cap, true, 0,
+                                                  (uint32_t*)(extra + row), (int32_t*)extra, p->stream);
+    if (e != hipSuccess) return hip_status(e, "nvrx_profiler_get_histograms: segment_histogram");
+    rc = ensure_small(p, span);
+    if (rc) return rc;
+    e = hipMemcpyAsync(p->h_small, extra, span, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) return hip_status(e, "nvrx_profiler_get_histograms: download");
+    const int32_t* hnum = (const int32_t*)p->h_small;
+    const uint32_t* hc = (const uint32_t*)(p->h_small + row);
+    std::vector<uint32_t> order;
+    for (int64_t s = 0; s < nslots; ++s)
+        if (hnum[s] > 0) order.push_back((uint32_t)s);
+    std::sort(order.begin(), order.end(),
+              [&](uint32_t a, uint32_t b) { return p->names[a] < p->names[b]; });
+    *count = (int64_t)order.size();
+    const int64_t m = std::min<int64_t>(cap_out, *count);
+    for (int64_t i = 0; i < m; ++i) {
+        if (slots) slots[i] = order[i];
+        if (num) num[i] = hnum[order[i]];
+        if (out)
+            std::memcpy(out + i * NVRX_HIST_BINS, hc + (size_t)order[i] * NVRX_HIST_BINS,
+                        NVRX_HIST_BINS * sizeof(uint32_t));
     }
     return NVRX_OK;
 }

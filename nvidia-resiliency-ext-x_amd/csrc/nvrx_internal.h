@@ -30,6 +30,14 @@ hipError_t segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off, 
                                     const int32_t* permille, int nq, float* out, int32_t* num,
                                     hipStream_t st);
 
+// fixed-bucket histograms (segment_histogram.hip): counts [nseg][NVRX_HIST_BINS], num [nseg] or NULL
+hipError_t segment_histogram_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
+                                     int64_t seg_begin, int64_t seg_len, int64_t cap, int accumulate,
+                                     uint32_t* counts, int32_t* num, hipStream_t st);
+hipError_t segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off, const int32_t* seg_len,
+                                    int64_t nseg, int64_t max_len, int64_t cap, bool aligned16,
+                                    int accumulate, uint32_t* counts, int32_t* num, hipStream_t st);
+
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 
 hipError_t kernel_ref(const int32_t* num, const float* med, int64_t R, int64_t K, float* ref,

@@ -28,6 +28,7 @@ NVRX_STATS_EXACT = 1
 NVRX_STATS_COLREF_READY = 0x10
 NVRX_MAX_SEGMENT = 1 << 30  # rings above 32,768 samples sort in device scratch
 NVRX_MAX_QUANTILES = 8  # quantiles (permilles) one nvrx_*_quantiles* call resolves
+HIST_BINS = 240  # NVRX_HIST_BINS: buckets of the fixed log-linear duration histogram
 NVRX_MAX_ATTRIBUTION = 16  # kernels per row one nvrx_score_attribution call returns
 NVRX_ATTR_RELATIVE = 0
 NVRX_ATTR_INDIVIDUAL = 1
@@ -104,6 +105,10 @@ SIGNATURES = {
                                                  ctypes.POINTER(StatsSoA), P, i64, P]),
     "nvrx_segment_quantiles_strided": (ctypes.c_int, [P, i64, i64, i64, i64, i64, P, i32, P, P, P]),
     "nvrx_segment_quantiles_ragged": (ctypes.c_int, [P, P, P, i64, i64, i64, i32, P, i32, P, P, P]),
+    "nvrx_histogram_bucket": (u32, [u32]),
+    "nvrx_histogram_edge": (ctypes.c_uint64, [i32]),
+    "nvrx_segment_histogram_strided": (ctypes.c_int, [P, i64, i64, i64, i64, i64, i32, P, P, P]),
+    "nvrx_segment_histogram_ragged": (ctypes.c_int, [P, P, P, i64, i64, i64, i32, i32, P, P, P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),
@@ -133,6 +138,7 @@ SIGNATURES = {
     "nvrx_profiler_kernel_name": (ctypes.c_int, [P, u32, ctypes.c_char_p, i64]),
     "nvrx_profiler_get_records": (ctypes.c_int, [P, i64, ctypes.POINTER(i64), P]),
     "nvrx_profiler_get_quantiles": (ctypes.c_int, [P, P, i32, i64, ctypes.POINTER(i64), P, P, P]),
+    "nvrx_profiler_get_histograms": (ctypes.c_int, [P, i64, ctypes.POINTER(i64), P, P, P]),
     "nvrx_profiler_capture_available": (ctypes.c_int, []),
     "nvrx_capture_flush": (ctypes.c_int, []),
     "nvrx_capture_stats": (ctypes.c_int, [ctypes.POINTER(CaptureCounters)]),

@@ -30,7 +30,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import histograms, ops
 
 
 # The per-kernel reference (min over ranks of MED) is fused into the stats epilogue as one
@@ -372,6 +372,22 @@ class MatrixReporter:
         self.compute_stats(ns, s_push)
         self.compute_scores()
         return self.land()
+
+    def histograms(self, ns: torch.Tensor, s_push: int, out: Optional[torch.Tensor] = None,
+                   accumulate: bool = False) -> torch.Tensor:
+        """Duration histograms of the matrix ``compute_stats`` takes, over the same retained
+        windows (the last ``cap`` of ``s_push`` samples per rank and kernel): an int32 device
+        tensor [R, K, 240] over the fixed buckets of ``straggler.histograms``.  ``out``: the
+        tensor to write, or with ``accumulate=True`` to add this interval's counts to.  The
+        buckets are shared, so ``out.sum(0, dtype=torch.int64)`` is the world's histogram per
+        kernel.  It reads ``ns`` only and changes none of the report's buffers; the call queues
+        behind reports still in flight.  Beyond the reference."""
+        self._order_after_inflight()
+        R, K = self.R, self.K
+        flat = None if out is None else out.view(R * K, histograms.BINS)
+        c = ops.segment_histogram_strided(ns.view(-1), R * K, s_push, 0, s_push, cap=self.cap,
+                                          out=flat, accumulate=accumulate)
+        return c.view(R, K, histograms.BINS)
 
     def attribute(self, top: int = 8, kind: str = "relative") -> BatchAttribution:
         """Which kernels made each rank's score what it is: per rank the `top` (1..16) kernels

@@ -262,6 +262,30 @@ class KernelProfiler:
         names = [self._name_of(int(s)) for s in slots[:m]]
         return names, num[:m], np.ascontiguousarray(q[:, :m])
 
+    def get_histograms(self):
+        """Per-kernel duration histograms (HIP) over the records the rings retain: ``(names, num,
+        counts)`` with names sorted, num the retained records per kernel and counts an int64 array
+        [len(names), 240] over the fixed buckets of ``histograms`` (``histograms.edges_us()``).
+        The buckets are the same on every rank and in every report, so counts add
+        (``histograms.merge``).  Beyond the reference; it leaves the records and ``get_stats`` as
+        they are, so call it before ``reset``."""
+        L = N.lib()
+        count = ctypes.c_int64()
+        N.check(L.nvrx_profiler_get_histograms(self._h, 0, ctypes.byref(count), None, None, None),
+                "get_histograms")
+        while True:
+            n = int(count.value)
+            slots = np.empty(n, np.uint32)
+            num = np.empty(n, np.int32)
+            c = np.empty((n, N.HIST_BINS), np.uint32)
+            N.check(L.nvrx_profiler_get_histograms(self._h, n, ctypes.byref(count), slots.ctypes.data,
+                                                   num.ctypes.data, c.ctypes.data), "get_histograms")
+            if int(count.value) <= n:
+                break
+        m = int(count.value)  # may have shrunk (a reset from another thread)
+        names = [self._name_of(int(s)) for s in slots[:m]]
+        return names, num[:m], c[:m].astype(np.int64)
+
     def get_records(self):
         """(slots u32, ns u32) of the device record log since the last reset, push order
         (nvrx_profiler_get_records) -- what the statistics are computed from."""
@@ -362,6 +386,12 @@ class CuptiManager:
         with self.lock:
             self._ensure_initialized()
             return self.cupti_ext.get_quantiles(permille)
+
+    def get_histograms(self):
+        """``KernelProfiler.get_histograms`` of the active run: (names, num, counts [n, 240])."""
+        with self.lock:
+            self._ensure_initialized()
+            return self.cupti_ext.get_histograms()
 
     def reset_results(self):
         with self.lock:

@@ -183,6 +183,71 @@ def segment_quantiles_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: O
     return out
 
 
+def _histogram_request(out, accumulate):
+    # checked first: no tensor is looked at
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs out, the counts to add to")
+
+
+def _histogram_outputs(nseg, device, out, num):
+    if out is None:
+        out = torch.empty((nseg, N.HIST_BINS), dtype=torch.int32, device=device)
+    N.require_device(out, "out")
+    if (out.dtype != torch.int32 or tuple(out.shape) != (nseg, N.HIST_BINS) or
+            not out.is_contiguous() or out.data_ptr() % 16):
+        raise ValueError("out must be a contiguous, 16-byte aligned int32 tensor of shape [nseg, 240]")
+    if num is not None:
+        N.require_device(num, "num")
+        if num.dtype != torch.int32 or num.numel() < nseg or not num.is_contiguous():
+            raise ValueError("num must be a contiguous int32 tensor of >= nseg elements")
+    return out
+
+
+def segment_histogram_strided(ns: torch.Tensor, nseg: int, seg_stride: int, seg_begin: int,
+                              seg_len: int, cap: int = 0, out: Optional[torch.Tensor] = None,
+                              num: Optional[torch.Tensor] = None, accumulate: bool = False,
+                              stream=None) -> torch.Tensor:
+    """Fixed-bucket duration histograms of the segments of ``segment_stats_strided`` (same
+    addressing, same ring retention): an int32 [nseg, 240] tensor of counts over the buckets of
+    ``histograms`` (the same edges for every segment, so counts add over ranks and reports).
+    ``out``: counts to write, or with ``accumulate=True`` to add to (then required); ``num``
+    (int32 [nseg], optional) receives the retained lengths.  An empty segment counts nothing."""
+    _histogram_request(out, accumulate)
+    N.require_device(ns, "ns")
+    if ns.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
+    if nseg > 0 and (nseg - 1) * seg_stride + seg_begin + seg_len > ns.numel():
+        raise ValueError("segments exceed the ns tensor")
+    out = _histogram_outputs(max(nseg, 0), ns.device, out, num)
+    N.call("nvrx_segment_histogram_strided", ns.data_ptr(), nseg, seg_stride, seg_begin, seg_len,
+           cap, int(bool(accumulate)), out.data_ptr(), N.ptr(num), _stream(stream))
+    return out
+
+
+def segment_histogram_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: Optional[torch.Tensor],
+                             max_len: int, cap: int = 0, aligned16: bool = False,
+                             out: Optional[torch.Tensor] = None, num: Optional[torch.Tensor] = None,
+                             accumulate: bool = False, stream=None) -> torch.Tensor:
+    """Histograms of the ragged segments of ``segment_stats_ragged`` (int32 [nseg, 240], as
+    ``segment_histogram_strided``); a segment with ``seg_len < 0`` is skipped (its outputs
+    untouched)."""
+    _histogram_request(out, accumulate)
+    N.require_device(ns, "ns")
+    N.require_device(seg_off, "seg_off")
+    if ns.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
+    nseg = seg_off.numel() - (0 if seg_len is not None else 1)
+    if seg_off.dtype != torch.int64 or (seg_len is not None and seg_len.dtype != torch.int32):
+        raise TypeError("seg_off must be int64 and seg_len int32")
+    if seg_len is not None:
+        N.require_device(seg_len, "seg_len")
+    out = _histogram_outputs(max(nseg, 0), ns.device, out, num)
+    N.call("nvrx_segment_histogram_ragged", ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len),
+           max(nseg, 0), max_len, cap, int(aligned16), int(bool(accumulate)), out.data_ptr(),
+           N.ptr(num), _stream(stream))
+    return out
+
+
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,
                scratch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """ref[k] = min_r med[r, k] if every row has k (num > 0), else NaN (reporting.py:255-296)."""

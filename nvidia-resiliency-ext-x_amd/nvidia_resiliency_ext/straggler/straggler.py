@@ -166,6 +166,22 @@ class Detector:
         return {n: tuple(float(x) for x in q[:, i]) for i, n in enumerate(names)}
 
     @classmethod
+    def kernel_histograms(cls) -> Dict[str, np.ndarray]:
+        """Duration histograms of every kernel captured in the current report interval:
+        composite kernel name -> int64 counts [240] over the fixed log-linear buckets of
+        ``straggler.histograms`` (``histograms.edges_us()`` gives the edges in us).  The buckets
+        are the same on every rank and in every report, so the counts of a kernel add over ranks
+        and over intervals (``histograms.merge``), and ``histograms.quantile_bounds`` brackets any
+        quantile of the sum.  Beyond the reference.  Call it BEFORE ``generate_report``, which
+        resets the profiler results (afterwards the interval is empty and this returns {}).  It
+        changes neither the report, nor the scores, nor any collective."""
+        assert cls.initialized
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        names, _, counts = cls.cupti_manager.get_histograms()
+        return {n: counts[i].copy() for i, n in enumerate(names)}
+
+    @classmethod
     def kernel_attribution(cls, top: int = 8, kind: str = "relative"):
         """The kernels behind this rank's GPU score in the LAST report: a list of at most `top`
         (1..16) ``KernelAttribution(name, score, loss_us, share)``, largest loss first, where
