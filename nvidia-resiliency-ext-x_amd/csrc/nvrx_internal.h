@@ -80,7 +80,7 @@ hipError_t records_ingest(nvrx_record* dst, const nvrx_record* src, int64_t n, u
 hipError_t records_unbucket(const int64_t* seg_off, const int32_t* seg_len, const int64_t* dst_off,
                             const uint32_t* ns, int64_t nslots, nvrx_record* out, hipStream_t st);
 
-// abi.cpp <-> capture.cpp
+// abi.cpp (the thread-local message) and profiler.cpp (the handle) <-> capture.cpp
 #include <string>
 void set_error(const std::string& msg);
 // one completed dispatch: what the reference's composite key is built from

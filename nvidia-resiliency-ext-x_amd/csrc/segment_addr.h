@@ -1,5 +1,6 @@
-// segment_addr.h -- where a segment lies in memory (strided, ragged), the fused column
-// reference and the empty result: what every statistics kernel takes as arguments.
+// segment_addr.h -- where a segment lies in memory (strided, ragged), what a launch over such
+// segments has to be sized for, the fused column reference and the empty result: what every
+// segment kernel takes as arguments.
 #pragma once
 #include "nvrx_common.h"
 #include "nvrx_internal.h"
@@ -35,6 +36,31 @@ struct RaggedSegs {  // segment s = base[off[s] : off[s] + len[s]] (len NULL: of
         return (int)((cap > 0 && len > cap) ? cap : len);
     }
 };
+
+// need = retained length + offset in the first 16-byte vector: what a wave has to hold
+__device__ __forceinline__ int seg_need(const uint32_t* p, int n) {
+    return n + (int)(((uintptr_t)p & 15) >> 2);
+}
+
+// Host side, before a launch: keep = the longest retained length, [need_lo, need_hi] = the range
+// every segment's need lies in, aligned = every retained run starts on a 16-byte boundary.
+struct SegRange {
+    int64_t keep, need_lo, need_hi;
+    bool aligned;
+};
+inline int64_t seg_keep(int64_t len, int64_t cap) { return (cap > 0 && len > cap) ? cap : len; }
+// every strided segment has the same length and phase
+inline SegRange seg_range(const StridedSegs& g) {
+    const int64_t keep = seg_keep(g.len, g.cap);
+    const bool aligned = ((g.stride % 4) == 0) &&
+                         ((((uintptr_t)(g.base + g.begin + (g.len - keep))) & 15) == 0);
+    return {keep, keep, aligned ? keep : keep + 3, aligned};
+}
+// ragged segments of at most max_len samples; aligned16: the caller's word for every run
+inline SegRange seg_range(const RaggedSegs& g, int64_t max_len, bool aligned16) {
+    const int64_t keep = seg_keep(max_len, g.cap);
+    return {keep, 0, aligned16 ? keep : keep + 3, aligned16};
+}
 
 // Optional fused per-column reference (segment s = row s / ncols, column s % ncols):
 // minbits[c] = atomicMin of the float bits of MED (non-negative floats order like their

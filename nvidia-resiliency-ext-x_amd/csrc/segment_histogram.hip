@@ -118,11 +118,6 @@ __device__ __forceinline__ void store_bins(uint32_t* counts, int64_t s, int t, u
     *o = c;
 }
 
-// need = retained length + offset in the first 16-byte vector
-__device__ __forceinline__ int seg_need(const uint32_t* p, int n) {
-    return n + (int)(((uintptr_t)p & 15) >> 2);
-}
-
 constexpr int WV = 4;  // vectors per lane per trip
 
 template <class Segs>
@@ -255,16 +250,14 @@ hipError_t launch_histogram(const Segs& segs, int64_t nseg, int64_t need_lo, int
 
 }  // namespace
 
-// Shape checks happen in abi.cpp before these run.
+// Shape checks happen in abi.cpp (check_strided / check_ragged) before these run.
 hipError_t segment_histogram_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
                                      int64_t seg_begin, int64_t seg_len, int64_t cap, int accumulate,
                                      uint32_t* counts, int32_t* num, hipStream_t st) {
     if (nseg <= 0) return hipSuccess;
     StridedSegs segs{ns, seg_stride, seg_begin, seg_len, cap};
-    const int64_t keep = (cap > 0 && seg_len > cap) ? cap : seg_len;
-    const bool aligned = ((seg_stride % 4) == 0) &&
-                         ((((uintptr_t)(ns + seg_begin + (seg_len - keep))) & 15) == 0);
-    return launch_histogram(segs, nseg, keep, aligned ? keep : keep + 3, accumulate, counts, num, st);
+    const SegRange r = seg_range(segs);
+    return launch_histogram(segs, nseg, r.need_lo, r.need_hi, accumulate, counts, num, st);
 }
 
 hipError_t segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off, const int32_t* seg_len,
@@ -272,8 +265,8 @@ hipError_t segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off, 
                                     int accumulate, uint32_t* counts, int32_t* num, hipStream_t st) {
     if (nseg <= 0) return hipSuccess;
     RaggedSegs segs{ns, seg_off, seg_len, cap};
-    const int64_t keep = (cap > 0 && max_len > cap) ? cap : max_len;
-    return launch_histogram(segs, nseg, 0, aligned16 ? keep : keep + 3, accumulate, counts, num, st);
+    const SegRange r = seg_range(segs, max_len, aligned16);
+    return launch_histogram(segs, nseg, r.need_lo, r.need_hi, accumulate, counts, num, st);
 }
 
 }  // namespace nvrx

@@ -231,10 +231,6 @@ __device__ __forceinline__ unsigned quant_core(unsigned (&v)[PL], int n, int m0,
     return res;
 }
 
-// need = retained length + offset in the first 16-byte vector: what a wave has to hold
-__device__ __forceinline__ int seg_need(const uint32_t* p, int n) {
-    return n + (int)(((uintptr_t)p & 15) >> 2);
-}
 constexpr int QUANT_WAVE_MAX = 64 * 128;  // the longest need of the register path
 
 // Register path, class PL: segments of 32 * PL < need <= 64 * PL (PL = 4: every need <= 256,
@@ -391,17 +387,15 @@ hipError_t launch_quantiles(const Segs& segs, int64_t nseg, int64_t need_lo, int
 
 }  // namespace
 
-// Shape checks happen in abi.cpp before these run.
+// Shape checks happen in abi.cpp (check_strided / check_ragged) before these run.
 hipError_t segment_quantiles_strided(const uint32_t* ns, int64_t nseg, int64_t seg_stride,
                                      int64_t seg_begin, int64_t seg_len, int64_t cap,
                                      const int32_t* permille, int nq, float* out, int32_t* num,
                                      hipStream_t st) {
     if (nseg <= 0) return hipSuccess;
     StridedSegs segs{ns, seg_stride, seg_begin, seg_len, cap};
-    const int64_t keep = (cap > 0 && seg_len > cap) ? cap : seg_len;
-    const bool aligned = ((seg_stride % 4) == 0) &&
-                         ((((uintptr_t)(ns + seg_begin + (seg_len - keep))) & 15) == 0);
-    return launch_quantiles(segs, nseg, keep, aligned ? keep : keep + 3, permille, nq, out, num, st);
+    const SegRange r = seg_range(segs);
+    return launch_quantiles(segs, nseg, r.need_lo, r.need_hi, permille, nq, out, num, st);
 }
 
 hipError_t segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off, const int32_t* seg_len,
@@ -410,8 +404,8 @@ hipError_t segment_quantiles_ragged(const uint32_t* ns, const int64_t* seg_off, 
                                     hipStream_t st) {
     if (nseg <= 0) return hipSuccess;
     RaggedSegs segs{ns, seg_off, seg_len, cap};
-    const int64_t keep = (cap > 0 && max_len > cap) ? cap : max_len;
-    return launch_quantiles(segs, nseg, 0, aligned16 ? keep : keep + 3, permille, nq, out, num, st);
+    const SegRange r = seg_range(segs, max_len, aligned16);
+    return launch_quantiles(segs, nseg, r.need_lo, r.need_hi, permille, nq, out, num, st);
 }
 
 }  // namespace nvrx

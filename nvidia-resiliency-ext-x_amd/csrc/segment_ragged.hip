@@ -246,10 +246,11 @@ static hipError_t ragged_join(hipStream_t st, Fork* f) {
 // The class kernels over the class-ordered segment list: keep = the longest retained segment;
 // classes it rules out are not launched.
 static hipError_t ragged_launch_classes(const RaggedSegs& segs, const uint32_t* cls_list,
-                                        const uint32_t* cls, int64_t keep, bool aligned16, bool exact,
+                                        const uint32_t* cls, const SegRange& r, bool exact,
                                         const nvrx_stats_soa& out, hipStream_t st) {
     const uint32_t* list = cls_list;
-    const int64_t need = aligned16 ? keep : keep + 3;
+    const int64_t keep = r.keep, need = r.need_hi;
+    const bool aligned16 = r.aligned;
     // class kernels; classes that max_len rules out are not launched.  With side streams the
     // classes are dealt round robin over them in launch order (fork / join by events, which HIP
     // graph capture follows), so one class's tail and latency-bound waves overlap the next class.
@@ -301,7 +302,8 @@ hipError_t segment_stats_ragged(const uint32_t* ns, const int64_t* seg_off, cons
     };
     if (nseg <= 0) return colref();
     RaggedSegs segs{ns, seg_off, seg_len, cap};
-    const int64_t keep = (cap > 0 && max_len > cap) ? cap : max_len;
+    const SegRange r = seg_range(segs, max_len, aligned16);
+    const int64_t keep = r.keep;
     if (keep > NVRX_MAX_SEGMENT) return hipErrorInvalidValue;
     const bool exact = mode == NVRX_STATS_EXACT;
     if (nseg >= ((int64_t)1 << 32) - ((int64_t)1 << 26)) return hipErrorInvalidValue;  // 32-bit lists
@@ -326,7 +328,7 @@ hipError_t segment_stats_ragged(const uint32_t* ns, const int64_t* seg_off, cons
                        cls);
     hipLaunchKernelGGL(classify_scatter_kernel, dim3((unsigned)nblocks), dim3(CLS_THREADS), 0, st,
                        segs, nseg, chunk, aligned16 ? 1 : 0, exact ? 1 : 0, full_len(keep, aligned16, exact), bcnt, list);
-    const hipError_t e = ragged_launch_classes(segs, list, cls, keep, aligned16, exact, out, st);
+    const hipError_t e = ragged_launch_classes(segs, list, cls, r, exact, out, st);
     const hipError_t f = hipFreeAsync(ws, st);  // on the error path too
     if (e != hipSuccess) return e;
     if (f != hipSuccess) return f;

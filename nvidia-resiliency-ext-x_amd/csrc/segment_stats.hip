@@ -253,14 +253,11 @@ hipError_t segment_stats_strided(const uint32_t* ns, int64_t nseg, int64_t seg_s
     if (hipError_t e = make_colref(col_ref, ncols, st, cr, ready); e != hipSuccess) return e;
     if (nseg <= 0) return hipSuccess;
     StridedSegs segs{ns, seg_stride, seg_begin, seg_len, cap};
-    const int64_t keep = (cap > 0 && seg_len > cap) ? cap : seg_len;
-    if (keep > NVRX_MAX_SEGMENT) return hipErrorInvalidValue;
-    const bool aligned = ((seg_stride % 4) == 0) &&
-                         ((((uintptr_t)(ns + seg_begin + (seg_len - keep))) & 15) == 0);
-    const int64_t need = aligned ? keep : keep + 3;
-    if (mode == NVRX_STATS_EXACT || need > 64 * 128) return launch_exact(segs, nseg, keep, out, cr, st);
+    const SegRange r = seg_range(segs);
+    if (r.keep > NVRX_MAX_SEGMENT) return hipErrorInvalidValue;
+    if (mode == NVRX_STATS_EXACT || r.need_hi > 64 * 128) return launch_exact(segs, nseg, r.keep, out, cr, st);
     // every strided segment has the same length and (aligned) phase
-    return launch_fast(segs, nseg, need, aligned ? keep : -1, out, cr, st);
+    return launch_fast(segs, nseg, r.need_hi, r.aligned ? r.keep : -1, out, cr, st);
 }
 
 // raw u32 ns (durations below 2^32 ns, never encoded) -> duration keys, in place: values from

@@ -207,30 +207,32 @@ class KernelProfiler:
         N.call("nvrx_profiler_saturated", self._h, ctypes.byref(c))
         return int(c.value)
 
+    def _sized_query(self, what, call, payload):
+        """The size-query protocol of the per-kernel getters.  ``call(cap_out, count_ref, slots,
+        num, *payload)`` makes the C call, ``payload(n)`` allocates its output arrays for n
+        kernels.  The first call (n = 0) only asks for the count; a count that grew since
+        (records arrived in between) retries, one that shrank (a reset from another thread) means
+        only ``m`` entries were written.  Returns (names, num[:m], payload arrays, m)."""
+        count = ctypes.c_int64()
+        n = 0
+        while True:
+            slots, num, arrays = np.empty(n, np.uint32), np.empty(n, np.int32), payload(n)
+            N.check(call(n, ctypes.byref(count), slots.ctypes.data, num.ctypes.data,
+                         *(a.ctypes.data for a in arrays)), what)
+            if int(count.value) <= n:
+                break
+            n = int(count.value)
+        m = int(count.value)
+        return [self._name_of(int(s)) for s in slots[:m]], num[:m], arrays, m
+
     def get_stats_columns(self) -> KernelSummaries:
         """Per-kernel statistics (HIP) as columns, sorted by composite kernel name.  One
         device computation: the size query's result is cached by the library and the copying
-        call reuses it (recomputed only if records arrived in between, hence the loop)."""
-        L = N.lib()
-        count = ctypes.c_int64()
-        N.call("nvrx_profiler_get_stats", self._h, 0, ctypes.byref(count), None, None, None,
-               None, None, None, None)
-        p = lambda a: a.ctypes.data  # noqa: E731
-        while True:
-            n = int(count.value)
-            slots = np.empty(n, np.uint32)
-            num = np.empty(n, np.int32)
-            cols = [np.empty(n, np.float32) for _ in range(5)]
-            N.check(L.nvrx_profiler_get_stats(self._h, n, ctypes.byref(count), p(slots), p(num),
-                                              *(p(c) for c in cols)), "get_stats")
-            if int(count.value) <= n:
-                break
-        # the count may also have shrunk (a reset from another thread): only count.value
-        # entries were written
-        m = int(count.value)
-        slots, num, cols = slots[:m], num[:m], [c[:m] for c in cols]
-        names = [self._name_of(int(s)) for s in slots]
-        return KernelSummaries(names, num, *cols)
+        call reuses it (recomputed only if records arrived in between)."""
+        names, num, cols, m = self._sized_query(
+            "get_stats", lambda *a: N.lib().nvrx_profiler_get_stats(self._h, *a),
+            lambda n: [np.empty(n, np.float32) for _ in range(5)])
+        return KernelSummaries(names, num, *(c[:m] for c in cols))
 
     def get_quantiles(self, permille):
         """Per-kernel duration quantiles (HIP) over the records the rings retain: ``(names, num,
@@ -243,24 +245,10 @@ class KernelProfiler:
         from .ops import permille_array
 
         pm = permille_array(permille)
-        nq = len(pm)
-        L = N.lib()
-        count = ctypes.c_int64()
-        N.check(L.nvrx_profiler_get_quantiles(self._h, pm, nq, 0, ctypes.byref(count), None, None,
-                                              None), "get_quantiles")
-        while True:
-            n = int(count.value)
-            slots = np.empty(n, np.uint32)
-            num = np.empty(n, np.int32)
-            q = np.empty((nq, n), np.float32)
-            N.check(L.nvrx_profiler_get_quantiles(self._h, pm, nq, n, ctypes.byref(count),
-                                                  slots.ctypes.data, num.ctypes.data,
-                                                  q.ctypes.data), "get_quantiles")
-            if int(count.value) <= n:
-                break
-        m = int(count.value)  # may have shrunk (a reset from another thread)
-        names = [self._name_of(int(s)) for s in slots[:m]]
-        return names, num[:m], np.ascontiguousarray(q[:, :m])
+        names, num, (q,), m = self._sized_query(
+            "get_quantiles", lambda *a: N.lib().nvrx_profiler_get_quantiles(self._h, pm, len(pm), *a),
+            lambda n: [np.empty((len(pm), n), np.float32)])
+        return names, num, np.ascontiguousarray(q[:, :m])
 
     def get_histograms(self):
         """Per-kernel duration histograms (HIP) over the records the rings retain: ``(names, num,
@@ -269,22 +257,10 @@ class KernelProfiler:
         The buckets are the same on every rank and in every report, so counts add
         (``histograms.merge``).  Beyond the reference; it leaves the records and ``get_stats`` as
         they are, so call it before ``reset``."""
-        L = N.lib()
-        count = ctypes.c_int64()
-        N.check(L.nvrx_profiler_get_histograms(self._h, 0, ctypes.byref(count), None, None, None),
-                "get_histograms")
-        while True:
-            n = int(count.value)
-            slots = np.empty(n, np.uint32)
-            num = np.empty(n, np.int32)
-            c = np.empty((n, N.HIST_BINS), np.uint32)
-            N.check(L.nvrx_profiler_get_histograms(self._h, n, ctypes.byref(count), slots.ctypes.data,
-                                                   num.ctypes.data, c.ctypes.data), "get_histograms")
-            if int(count.value) <= n:
-                break
-        m = int(count.value)  # may have shrunk (a reset from another thread)
-        names = [self._name_of(int(s)) for s in slots[:m]]
-        return names, num[:m], c[:m].astype(np.int64)
+        names, num, (c,), m = self._sized_query(
+            "get_histograms", lambda *a: N.lib().nvrx_profiler_get_histograms(self._h, *a),
+            lambda n: [np.empty((n, N.HIST_BINS), np.uint32)])
+        return names, num, c[:m].astype(np.int64)
 
     def get_records(self):
         """(slots u32, ns u32) of the device record log since the last reset, push order

@@ -53,6 +53,36 @@ def _stream(stream):
     return N.stream_handle(stream)
 
 
+def _check_strided(ns, nseg, seg_stride, seg_begin, seg_len):
+    """The strided triple of every segment_*_strided call: device u32 keys holding all segments."""
+    N.require_device(ns, "ns")
+    if ns.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
+    if nseg > 0 and (nseg - 1) * seg_stride + seg_begin + seg_len > ns.numel():
+        raise ValueError("segments exceed the ns tensor")
+
+
+def _check_ragged(ns, seg_off, seg_len) -> int:
+    """The ragged triple of every segment_*_ragged call; returns nseg (seg_len None: seg_off
+    holds nseg + 1 offsets)."""
+    N.require_device(ns, "ns")
+    N.require_device(seg_off, "seg_off")
+    if ns.dtype not in (torch.int32, torch.uint32):
+        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
+    if seg_off.dtype != torch.int64 or (seg_len is not None and seg_len.dtype != torch.int32):
+        raise TypeError("seg_off must be int64 and seg_len int32")
+    if seg_len is not None:
+        N.require_device(seg_len, "seg_len")
+    return seg_off.numel() - (0 if seg_len is not None else 1)
+
+
+def _num_output(num, nseg):
+    if num is not None:
+        N.require_device(num, "num")
+        if num.dtype != torch.int32 or num.numel() < nseg or not num.is_contiguous():
+            raise ValueError("num must be a contiguous int32 tensor of >= nseg elements")
+
+
 def segment_stats_strided(ns: torch.Tensor, nseg: int, seg_stride: int, seg_begin: int,
                           seg_len: int, cap: int = 0, mode: int = STATS_FAST,
                           out: Optional[SegmentStats] = None, col_ref: Optional[torch.Tensor] = None,
@@ -61,11 +91,7 @@ def segment_stats_strided(ns: torch.Tensor, nseg: int, seg_stride: int, seg_begi
     ``_native.duration_keys``: plain ns below 3.76 s -- raw u32 ns of 3.76 s and more need
     ``encode_ns_u32_`` first; a u32 above ``_native.KEY_MAX`` comes from no u64 duration), last
     `cap` samples retained (CircularBuffer.h:53-69).  reference: CuptiProfiler.cpp:44-74."""
-    N.require_device(ns, "ns")
-    if ns.dtype not in (torch.int32, torch.uint32):
-        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
-    if nseg > 0 and (nseg - 1) * seg_stride + seg_begin + seg_len > ns.numel():
-        raise ValueError("segments exceed the ns tensor")
+    _check_strided(ns, nseg, seg_stride, seg_begin, seg_len)
     if out is None:
         out = SegmentStats.empty(nseg, ns.device)
     soa = out.soa()
@@ -95,11 +121,7 @@ def segment_stats_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: Optio
                          ncols: int = 0, stream=None) -> SegmentStats:
     """Stats of ragged segments; segments of <= 128 retained samples are bit-exact in every
     field.  col_ref ([2*ncols] int32): fused per-column reference, as for the strided call."""
-    N.require_device(ns, "ns")
-    N.require_device(seg_off, "seg_off")
-    nseg = seg_off.numel() - (0 if seg_len is not None else 1)
-    if seg_off.dtype != torch.int64 or (seg_len is not None and seg_len.dtype != torch.int32):
-        raise TypeError("seg_off must be int64 and seg_len int32")
+    nseg = _check_ragged(ns, seg_off, seg_len)
     if out is None:
         out = SegmentStats.empty(max(nseg, 0), ns.device)
     soa = out.soa()
@@ -130,10 +152,7 @@ def _quantile_outputs(nq, nseg, device, out, num):
     N.require_device(out, "out")
     if out.dtype != torch.float32 or tuple(out.shape) != (nq, nseg) or not out.is_contiguous():
         raise ValueError("out must be a contiguous float32 tensor of shape [nq, nseg]")
-    if num is not None:
-        N.require_device(num, "num")
-        if num.dtype != torch.int32 or num.numel() < nseg or not num.is_contiguous():
-            raise ValueError("num must be a contiguous int32 tensor of >= nseg elements")
+    _num_output(num, nseg)
     return out
 
 
@@ -148,11 +167,7 @@ def segment_quantiles_strided(ns: torch.Tensor, nseg: int, seg_stride: int, seg_
     interpolation (0 -> MIN, 1000 -> MAX, 500 of an odd n -> MED, bit for bit); NaN for an empty
     segment.  ``num`` (int32 [nseg], optional) receives the retained lengths."""
     pm = permille_array(permille)
-    N.require_device(ns, "ns")
-    if ns.dtype not in (torch.int32, torch.uint32):
-        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
-    if nseg > 0 and (nseg - 1) * seg_stride + seg_begin + seg_len > ns.numel():
-        raise ValueError("segments exceed the ns tensor")
+    _check_strided(ns, nseg, seg_stride, seg_begin, seg_len)
     out = _quantile_outputs(len(pm), max(nseg, 0), ns.device, out, num)
     N.call("nvrx_segment_quantiles_strided", ns.data_ptr(), nseg, seg_stride, seg_begin, seg_len,
            cap, pm, len(pm), out.data_ptr(), N.ptr(num), _stream(stream))
@@ -167,15 +182,7 @@ def segment_quantiles_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: O
     ``segment_quantiles_strided``); every segment is read by its own retained length, a
     segment with ``seg_len < 0`` is skipped (its outputs untouched)."""
     pm = permille_array(permille)
-    N.require_device(ns, "ns")
-    N.require_device(seg_off, "seg_off")
-    if ns.dtype not in (torch.int32, torch.uint32):
-        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
-    nseg = seg_off.numel() - (0 if seg_len is not None else 1)
-    if seg_off.dtype != torch.int64 or (seg_len is not None and seg_len.dtype != torch.int32):
-        raise TypeError("seg_off must be int64 and seg_len int32")
-    if seg_len is not None:
-        N.require_device(seg_len, "seg_len")
+    nseg = _check_ragged(ns, seg_off, seg_len)
     out = _quantile_outputs(len(pm), max(nseg, 0), ns.device, out, num)
     N.call("nvrx_segment_quantiles_ragged", ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len),
            max(nseg, 0), max_len, cap, int(aligned16), pm, len(pm), out.data_ptr(), N.ptr(num),
@@ -196,10 +203,7 @@ def _histogram_outputs(nseg, device, out, num):
     if (out.dtype != torch.int32 or tuple(out.shape) != (nseg, N.HIST_BINS) or
             not out.is_contiguous() or out.data_ptr() % 16):
         raise ValueError("out must be a contiguous, 16-byte aligned int32 tensor of shape [nseg, 240]")
-    if num is not None:
-        N.require_device(num, "num")
-        if num.dtype != torch.int32 or num.numel() < nseg or not num.is_contiguous():
-            raise ValueError("num must be a contiguous int32 tensor of >= nseg elements")
+    _num_output(num, nseg)
     return out
 
 
@@ -213,11 +217,7 @@ def segment_histogram_strided(ns: torch.Tensor, nseg: int, seg_stride: int, seg_
     ``out``: counts to write, or with ``accumulate=True`` to add to (then required); ``num``
     (int32 [nseg], optional) receives the retained lengths.  An empty segment counts nothing."""
     _histogram_request(out, accumulate)
-    N.require_device(ns, "ns")
-    if ns.dtype not in (torch.int32, torch.uint32):
-        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
-    if nseg > 0 and (nseg - 1) * seg_stride + seg_begin + seg_len > ns.numel():
-        raise ValueError("segments exceed the ns tensor")
+    _check_strided(ns, nseg, seg_stride, seg_begin, seg_len)
     out = _histogram_outputs(max(nseg, 0), ns.device, out, num)
     N.call("nvrx_segment_histogram_strided", ns.data_ptr(), nseg, seg_stride, seg_begin, seg_len,
            cap, int(bool(accumulate)), out.data_ptr(), N.ptr(num), _stream(stream))
@@ -232,15 +232,7 @@ def segment_histogram_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: O
     ``segment_histogram_strided``); a segment with ``seg_len < 0`` is skipped (its outputs
     untouched)."""
     _histogram_request(out, accumulate)
-    N.require_device(ns, "ns")
-    N.require_device(seg_off, "seg_off")
-    if ns.dtype not in (torch.int32, torch.uint32):
-        raise TypeError("ns must be a 32-bit integer tensor of duration keys")
-    nseg = seg_off.numel() - (0 if seg_len is not None else 1)
-    if seg_off.dtype != torch.int64 or (seg_len is not None and seg_len.dtype != torch.int32):
-        raise TypeError("seg_off must be int64 and seg_len int32")
-    if seg_len is not None:
-        N.require_device(seg_len, "seg_len")
+    nseg = _check_ragged(ns, seg_off, seg_len)
     out = _histogram_outputs(max(nseg, 0), ns.device, out, num)
     N.call("nvrx_segment_histogram_ragged", ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len),
            max(nseg, 0), max_len, cap, int(aligned16), int(bool(accumulate)), out.data_ptr(),

@@ -7,7 +7,7 @@ import torch
 
 import oracle as O
 from _fastbars import check_avg_std
-from nvidia_resiliency_ext.straggler import cupti, ops
+from nvidia_resiliency_ext.straggler import cupti, histograms, ops
 
 pytestmark = pytest.mark.gpu
 
@@ -108,6 +108,54 @@ def test_profiler_stats_bit_exact_and_name_sorted(profiler):
     assert "ignored_while_stopped" not in profiler.get_stats()
     profiler.reset()
     assert profiler.get_stats() == {}
+
+
+def test_one_report_pass_behind_all_three_getters():
+    # statistics, quantiles and histograms share one pass over the record log: one handle, the
+    # getters interleaved so the work buffer holds a larger result area after a smaller one and
+    # back.  1 record (one sample), 130 (just past the lane-per-segment classes), 300 (an
+    # overflowed ring of 256); names sort differently from their registration order; a fourth
+    # kernel is registered and never pushed.
+    cap = 256
+    rng = np.random.default_rng(cap)
+    one, mid, long_ = "zeta_blk_64_1_1_grid_8_1_1", "alpha_blk_256_1_1_grid_1_1_1", "mid_k"
+    data = {n: rng.integers(1000, 900_000, size=k, dtype=np.uint32)
+            for n, k in ((one, 1), (mid, 130), (long_, 300))}
+    names = sorted(data)
+    bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)  # noqa: E731
+    fields = ("num", "min", "max", "med", "avg", "std")
+    p = cupti.KernelProfiler(statsMaxLenPerKernel=cap, exact=True)
+    try:
+        p.initialize()
+        p.start()
+        for n, d in data.items():
+            p.push(n, d)
+        p.register_kernel("never_pushed_blk_1_1_1_grid_1_1_1")
+        for extra in (None, np.array([777_777], np.uint32)):
+            if extra is not None:
+                p.push(mid, extra)
+                data[mid] = np.concatenate([data[mid], extra])
+            s1 = p.get_stats_columns()
+            qn, qnum, q = p.get_quantiles((0, 500, 1000))
+            hn, hnum, h = p.get_histograms()
+            s2 = p.get_stats_columns()
+            assert s1.names == qn == hn == names  # sorted, without the empty kernel
+            want = [min(data[n].size, cap) for n in names]
+            assert s1.num.tolist() == qnum.tolist() == hnum.tolist() == want
+            assert np.array_equal(bits(q[0]), bits(s1.min))
+            assert np.array_equal(bits(q[2]), bits(s1.max))
+            i1 = names.index(one)
+            assert bits(q[1])[i1] == bits(s1.med)[i1]
+            for i, n in enumerate(names):
+                assert h[i].sum() == want[i]
+                assert np.array_equal(h[i], np.bincount(histograms.bucket_of(data[n][-cap:]),
+                                                        minlength=240))
+                got = (int(s1.num[i]),) + tuple(np.float32(getattr(s1, f)[i]) for f in fields[1:])
+                assert got == _oracle_slot_stats(data[n], cap), n
+            for f in fields:  # the cached result, untouched by the other two getters
+                assert getattr(s1, f).tobytes() == getattr(s2, f).tobytes(), f
+    finally:
+        p.close()
 
 
 def test_profiler_ring_cap_seven():
