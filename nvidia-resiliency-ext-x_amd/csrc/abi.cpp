@@ -241,7 +241,7 @@ int nvrx_kernel_ref(const int32_t* num, const float* med, int64_t R, int64_t K, 
     NVRX_CHECK_ARG(R >= 0 && K >= 0, "nvrx_kernel_ref: negative size");
     NVRX_CHECK_ARG(K == 0 || (ref && scratch), "nvrx_kernel_ref: null ref/scratch");
     NVRX_CHECK_ARG(R == 0 || K == 0 || (num && med), "nvrx_kernel_ref: null num/med");
-    NVRX_CHECK_ARG((R + 63) / 64 < 65536, "nvrx_kernel_ref: too many rows");
+    NVRX_CHECK_ARG(R <= NVRX_KREF_MAX_R, "nvrx_kernel_ref: too many rows");
     return hip_status(nvrx::kernel_ref(num, med, R, K, ref, scratch, S(stream)), "nvrx_kernel_ref");
 }
 
@@ -250,7 +250,7 @@ int nvrx_pack_min_times(const double* med, const int32_t* ids, int64_t n, float*
     NVRX_CHECK_ARG(n >= 0 && total >= 0, "nvrx_pack_min_times: negative size");
     NVRX_CHECK_ARG(total == 0 || times, "nvrx_pack_min_times: null times");
     NVRX_CHECK_ARG(n == 0 || (med && ids), "nvrx_pack_min_times: null inputs");
-    NVRX_CHECK_ARG(n <= total, "nvrx_pack_min_times: more entries than the tensor holds");
+    NVRX_CHECK_ARG(n <= total, "nvrx_pack_min_times: n > total (more entries than the tensor holds)");
     return hip_status(nvrx::pack_min_times(med, ids, n, times, total, S(stream)),
                       "nvrx_pack_min_times");
 }
@@ -302,7 +302,8 @@ int nvrx_score_attribution(const nvrx_attribution_args* a, void* stream) {
 int nvrx_finalize_scores(const double* partials, int64_t R, int64_t nshards, int32_t round_f32,
                          double thr_rel, double thr_ind, double* gpu_rel, double* gpu_ind,
                          uint8_t* strag_rel, uint8_t* strag_ind, int32_t* err, void* stream) {
-    NVRX_CHECK_ARG(R >= 0 && nshards >= 1, "nvrx_finalize_scores: bad size");
+    NVRX_CHECK_ARG(R >= 0, "nvrx_finalize_scores: negative R");
+    NVRX_CHECK_ARG(nshards >= 1, "nvrx_finalize_scores: nshards must be at least 1");
     NVRX_CHECK_ARG(R == 0 || partials, "nvrx_finalize_scores: null partials");
     return hip_status(nvrx::finalize_scores(partials, R, nshards, round_f32, thr_rel, thr_ind,
                                             gpu_rel, gpu_ind, strag_rel, strag_ind, err, S(stream)),
@@ -334,7 +335,8 @@ int nvrx_section_stats(const double* vals, const int64_t* off, int64_t nsec, int
 }
 
 int nvrx_stragglers(const double* score, int64_t n, double thr, uint8_t* mask, void* stream) {
-    NVRX_CHECK_ARG(n >= 0 && (n == 0 || (score && mask)), "nvrx_stragglers: bad args");
+    NVRX_CHECK_ARG(n >= 0, "nvrx_stragglers: negative n");
+    NVRX_CHECK_ARG(n == 0 || (score && mask), "nvrx_stragglers: null score/mask");
     return hip_status(nvrx::stragglers(score, n, thr, mask, S(stream)), "nvrx_stragglers");
 }
 

@@ -40,6 +40,10 @@ hipError_t segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off, 
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 
+// kernel_ref puts NVRX_KREF_ROWS rows on each block of grid.y (at most 65535 blocks): the
+// launcher and nvrx_kernel_ref's row limit both come from these two
+#define NVRX_KREF_ROWS 32
+#define NVRX_KREF_MAX_R ((int64_t)NVRX_KREF_ROWS * 65535)
 hipError_t kernel_ref(const int32_t* num, const float* med, int64_t R, int64_t K, float* ref,
                       uint32_t* scratch, hipStream_t st);
 hipError_t pack_min_times(const double* med, const int32_t* ids, int64_t n, float* times,

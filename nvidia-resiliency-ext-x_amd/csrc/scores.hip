@@ -67,13 +67,14 @@ __global__ void kref_final_kernel(const uint32_t* minbits, const uint32_t* missi
 hipError_t kernel_ref(const int32_t* num, const float* med, int64_t R, int64_t K, float* ref,
                       uint32_t* scratch, hipStream_t st) {
     if (K <= 0) return hipSuccess;
+    if (R > NVRX_KREF_MAX_R) return hipErrorInvalidValue;  // grid.y
     uint32_t* minbits = scratch;
     uint32_t* missing = scratch + K;
     const unsigned kb = (unsigned)((K + 255) / 256);
     hipLaunchKernelGGL(kref_init_kernel, dim3(kb), dim3(256), 0, st, minbits, missing, K);
     if (R > 0) {
         // 32 rows per thread: R/32 atomics per column, grid >> 256 CUs at scale
-        const int64_t rows = 32;
+        const int64_t rows = NVRX_KREF_ROWS;
         const unsigned rb = (unsigned)((R + rows - 1) / rows);
         hipLaunchKernelGGL(kref_reduce_kernel, dim3(kb, rb), dim3(256), 0, st, num, med, R, K,
                            rows, minbits, missing);
@@ -98,6 +99,7 @@ __global__ void pack_times_kernel(const double* med, const int32_t* ids, int64_t
 
 hipError_t pack_min_times(const double* med, const int32_t* ids, int64_t n, float* times,
                           int64_t total, hipStream_t st) {
+    if (total <= 0 && n <= 0) return hipSuccess;  // nothing to launch: no device needed
     if (total > 0) {
         const int64_t gb = (total + 255) / 256;
         const unsigned g = (unsigned)(gb < 1024 ? gb : 1024);

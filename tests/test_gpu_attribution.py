@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from _mp import run_world
+from _score_ref import inputs
 from nvidia_resiliency_ext.straggler import batch, ops
 
 pytestmark = pytest.mark.gpu
@@ -90,31 +91,6 @@ def check(num, med, avg, *, top, kind, **kw):
     if kw.get("hist") is not None:  # read only
         assert np.array_equal(hist_after.view(np.uint8), kw["hist"].view(np.uint8)), tag
     return gi, gl, gs, gw
-
-
-def inputs(R, K, dt, seed):
-    """Seeded statistics with absent kernels, filtered columns and references of every kind."""
-    g = np.random.default_rng(seed)
-    num = g.integers(0, 40, (R, K)).astype(np.int32)
-    num[g.random((R, K)) < 0.1] = 0            # absent on that rank
-    num[g.random((R, K)) < 0.02] = -3          # <= 0 is absent too
-    med = g.uniform(1.0, 100.0, (R, K)).astype(dt)
-    avg = (med * g.uniform(0.9, 1.4, (R, K))).astype(dt)
-    col_valid = (g.random(K) > 0.1).astype(np.uint8)
-    perm = g.permutation(K).astype(np.int32)   # ref_index: the column's id in the reference
-    ref = np.empty(K, np.float32)
-    ref[perm] = (np.where(num > 0, med, np.inf).min(0) * g.uniform(0.4, 1.0, K)).astype(np.float32)
-    bad = g.random(K)
-    ref[perm[bad < 0.06]] = -1.0
-    ref[perm[(bad >= 0.06) & (bad < 0.12)]] = np.nan
-    ref[~np.isfinite(ref) & ~np.isnan(ref)] = np.nan  # a column absent everywhere
-    missing = (g.random(K) < 0.08).astype(np.uint32)
-    stride = K + 5                              # history rows longer than K, slots permuted
-    slot = g.permutation(stride)[:K].astype(np.int32)
-    hist = g.uniform(0.5, 200.0, (R, stride)).astype(dt)
-    hist[:, slot] = np.minimum(hist[:, slot], med)  # as the report's scores call leaves it
-    return dict(num=num, med=med, avg=avg, col_valid=col_valid, perm=perm, ref=ref, missing=missing,
-                stride=stride, slot=slot, hist=hist)
 
 
 # ------------------------------------------------------------------ kernel
