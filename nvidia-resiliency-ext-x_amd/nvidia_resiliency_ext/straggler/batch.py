@@ -20,17 +20,23 @@ and the history are shard-local and the only exchange is the [R][6] f64 partials
 """
 from __future__ import annotations
 
-import os
-import time
 import weakref
 from dataclasses import dataclass
-from functools import partial
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import histograms, ops
+from .host_wait import (SPIN_BOUND_US, SYNC_MODES, _wait, set_sync_mode,  # noqa: F401
+                        sync_mode, wait_event)
+
+
+def __getattr__(name: str):  # report_graphs imports this module: its names resolve on first use
+    if name in ("ReportGraph", "PipelinedReports", "PIPE_ALT_MAX_BYTES", "TIMED_SPIN_CYCLES", "STAGGER_FRAC"):
+        from . import report_graphs
+        return getattr(report_graphs, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 # The per-kernel reference (min over ranks of MED) is fused into the stats epilogue as one
@@ -39,62 +45,6 @@ from . import histograms, ops
 # (kernel_ref: 64 rows per thread, R/64 atomics per column) once R is in the hundreds
 # (measured on MI355X: 885k segments on 54 columns, 0.6 ms -> 4.3 ms fused).
 FUSED_REF_MAX_ROWS = 256
-
-
-# How the host waits for a report's results (they land in pinned host memory):
-#   "bounded" (default) -- poll the completion event for at most SPIN_BOUND_US, then block in
-#       hipEventSynchronize on a blocking-sync event: a report that lands within the bound
-#       skips the driver's wake-up latency, a longer one does not hold a host core (in a
-#       training process that calls this API every core belongs to the job; the reference's
-#       report path blocks too, straggler.py:234-235, CuptiProfiler.cpp:136-146);
-#   "spin" -- poll until done (bench.py: the wake-up latency is part of every timed report);
-#   "block" -- block at once.
-# NVRX_SYNC selects the mode per process; set_sync_mode() changes it at run time.
-SYNC_MODES = ("bounded", "spin", "block")
-SPIN_BOUND_US = float(os.environ.get("NVRX_SPIN_US", "50"))
-_sync_mode = os.environ.get("NVRX_SYNC", "") or "bounded"
-if _sync_mode not in SYNC_MODES:
-    raise ValueError(f"NVRX_SYNC={_sync_mode!r}: one of {SYNC_MODES}")
-
-
-def set_sync_mode(mode: str) -> str:
-    """Select how report results are waited for (SYNC_MODES); returns the previous mode."""
-    global _sync_mode
-    if mode not in SYNC_MODES:
-        raise ValueError(f"sync mode {mode!r}: one of {SYNC_MODES}")
-    prev, _sync_mode = _sync_mode, mode
-    return prev
-
-
-def sync_mode() -> str:
-    return _sync_mode
-
-
-def wait_event(ev, mode: Optional[str] = None, bound_us: Optional[float] = None) -> None:
-    """Wait until a recorded event has completed, in the current (or the given) sync mode.
-    `ev` needs query() and synchronize(); the blocking fallback blocks only if the event was
-    created with blocking=True (every event this module waits on is)."""
-    mode = mode or _sync_mode
-    if mode == "block":
-        ev.synchronize()
-        return
-    if mode == "spin":
-        while not ev.query():
-            pass
-        return
-    bound = SPIN_BOUND_US if bound_us is None else bound_us
-    deadline = time.perf_counter_ns() + int(bound * 1e3)
-    while not ev.query():
-        if time.perf_counter_ns() >= deadline:
-            ev.synchronize()
-            return
-
-
-def _wait(device) -> None:
-    """Wait for the device's current stream (wait_event on an event recorded on it)."""
-    ev = torch.cuda.Event(blocking=True)
-    ev.record(torch.cuda.current_stream(device))
-    wait_event(ev)
 
 
 @dataclass
@@ -440,10 +390,12 @@ class MatrixReporter:
         launch sequence -- reference init, stats, scores, result copy -- costs one graph
         launch instead of one host launch per operation).  1 GPU, or the stats phase only
         on N GPUs (the partials exchange stays an eager collective)."""
+        from .report_graphs import ReportGraph
         return ReportGraph(self, ns, s_push)
 
     def graph_records(self, recs: torch.Tensor, rec_off: torch.Tensor) -> "ReportGraph":
         """graph() over record streams resident in HBM (compute_stats_records captured)."""
+        from .report_graphs import ReportGraph
         return ReportGraph(self, None, 0, stats=lambda bufs: self.compute_stats_records(
             recs, rec_off, bufs=bufs))
 
@@ -457,6 +409,7 @@ class MatrixReporter:
         depth) -- e.g. a fresh matrix per report in flight.  An input must not be modified while
         a report that reads it is in flight: collect() raises if a torch in-place operation
         changed it (its version counter moved) between that report's submit() and collect()."""
+        from .report_graphs import PipelinedReports
         ins = list(ns) if isinstance(ns, (list, tuple)) else [ns]
         return PipelinedReports(
             self, [lambda bufs, x=x: self.compute_stats(x, s_push, bufs=bufs) for x in ins],
@@ -474,378 +427,10 @@ class MatrixReporter:
         classification and the class kernels -- side-stream fork / join and stream-ordered
         scratch included -- captured into the report graphs).  recs: one record tensor or a list
         of them (same layout, rec_off shared), as ns for pipelined()."""
+        from .report_graphs import PipelinedReports
         ins = list(recs) if isinstance(recs, (list, tuple)) else [recs]
         return PipelinedReports(
             self, [lambda bufs, r=r: self.compute_stats_records(r, rec_off, bufs=bufs) for r in ins],
             inputs=[(r, rec_off) for r in ins], stats_bytes=8 * ins[0].shape[0], timing=timing,
             mode=mode, depth=depth, timing_reps=timing_reps)
 
-
-class ReportGraph:
-    """HIP graphs over a MatrixReporter's fixed buffers.  1 GPU: ``full`` is the whole
-    report (column-reference init, segment statistics, scores + straggler masks, the
-    device-to-host copy of the packed results) and is what ``run()`` replays; the same work
-    is also captured as two halves, ``stats`` and ``rest``, for callers that record timing
-    events between them (``run_stats()`` + ``run_rest()``).  One graph instead of two saves
-    ~12 us per configs[1] report on MI355X (0.685 -> 0.673 ms, tools/ab_report_overhead.py).
-    N GPUs: ``stats`` only; the partials exchange stays an eager collective."""
-
-    def __init__(self, rep: MatrixReporter, ns: Optional[torch.Tensor], s_push: int, stats=None):
-        self.rep = rep
-        own = rep.own  # the graphs run over the reporter's own buffer set
-        if stats is None:  # the statistics phase (record streams: MatrixReporter.graph_records)
-            stats = lambda bufs: rep.compute_stats(ns, s_push, bufs=bufs)  # noqa: E731
-        _warm_up(rep, stats)
-        # the captured statistics phase trusts col_ref as the previous report's scores epilogue
-        # left it (colref_ready at capture): replays must pair it with the scores (run_rest),
-        # which run_stats checks against the reporter's flag -- kept current by every replay
-        self._needs_clean = own.clean
-        stats, copy_out = partial(stats, own), partial(rep._copy_out, rep.h_out)
-        self.stats = _capture(stats)
-        self.rest = self.full = None
-        if rep.exchange:
-            # N GPUs: the shard's partials and the combine (+ the result copy) as graphs too;
-            # only the all_gather of the partials between them runs eagerly
-            self.partials = _capture(rep._scores_partials)
-            self.finalize = _capture(rep._finalize, copy_out)
-        else:
-            self.rest = _capture(rep.compute_scores, copy_out)
-            self.full = _capture(stats, rep.compute_scores, copy_out)
-
-    def _check_clean(self) -> None:
-        if self._needs_clean and not self.rep.own.clean:
-            raise RuntimeError("ReportGraph: the statistics graph was captured to follow a scores "
-                               "phase (its epilogue re-initialises the column reference); the last "
-                               "statistics phase was not followed by run_rest()")
-
-    def _finish(self) -> BatchResult:
-        """After the scores were replayed: the flag, the wait, the host views."""
-        rep = self.rep
-        rep.own.clean = rep._fuse_ref()
-        _wait(rep.device)
-        return rep.own.unpack(rep.h_out)
-
-    def run_stats(self) -> None:
-        self._check_clean()
-        self.rep._order_after_inflight()
-        self.stats.replay()
-        self.rep.own.clean = False
-
-    def run_rest(self) -> BatchResult:
-        rep = self.rep
-        rep._order_after_inflight()
-        if self.rest is None:  # N GPUs: partials graph, eager all_gather, combine graph
-            self.partials.replay()
-            rep._exchange()
-            self.finalize.replay()
-        else:
-            self.rest.replay()
-        return self._finish()
-
-    def run(self) -> BatchResult:
-        if self.full is None:
-            self.run_stats()
-            return self.run_rest()
-        self._check_clean()
-        self.rep._order_after_inflight()
-        self.full.replay()
-        return self._finish()
-
-
-def _capture(*phases) -> torch.cuda.CUDAGraph:
-    """The phases (callables), run in order on the current stream, captured as one HIP graph."""
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for phase in phases:
-            phase()
-    return g
-
-
-def _warm_up(rep: MatrixReporter, stats, bufs: Optional[_ReportBuffers] = None) -> None:
-    """One eager report over a buffer set (None: the reporter's own) on a side stream
-    (first-launch setup outside any graph capture); stats(bufs) runs the statistics phase.  The
-    individual history is restored afterwards: the warm-up must not fold whatever the inputs hold
-    now into it (the graphs' reports advance it exactly as report() does)."""
-    d = rep.device
-    b = rep.own if bufs is None else bufs
-    rep._order_after_inflight()
-    saved = rep.hist.clone() if rep.hist is not None else None
-    side = torch.cuda.Stream(d)
-    side.wait_stream(torch.cuda.current_stream(d))
-    with torch.cuda.stream(side):
-        stats(b)
-        if not rep.exchange:
-            rep.compute_scores(bufs=b)
-        elif rep._fuse_ref():  # N GPUs: leave col_ref initialised without the exchange
-            b.col_ref[:rep.K].fill_(0x7F800000)
-            b.col_ref[rep.K:2 * rep.K].zero_()
-            b.clean = True
-        if saved is not None:
-            rep.hist.copy_(saved)
-    torch.cuda.current_stream(d).wait_stream(side)
-    torch.cuda.synchronize(d)
-
-
-# NVRX_PIPE_MODE (timing A/B; PipelinedReports(mode=...) overrides the default, "auto"): "alt" each
-# report on its own stream of two; "side" the statistics phases on one stream, the rest of every
-# report on another; "whole" one whole-report graph per report on the caller's stream (round 4)
-_PIPE_MODE = os.environ.get("NVRX_PIPE_MODE", "")
-# "auto": alt while a report's statistics phase reads at most this many bytes.  Two reports'
-# statistics kernels then overlap at their launch boundaries (one launch's ramp and tail, ~15-35
-# us) -- configs[1] (4.3 GB) 0.673-0.687 -> 0.638-0.651 ms per report (with the stagger below,
-# profiles/r05/pipe_modes.json); a longer phase gains
-# nothing there and loses to the two kernels sharing the GPU for their whole duration: configs[2]
-# (34 GB) 5.57 ms whole, 5.65 side, 5.79 alt (profiles/r05/pipe_modes.json).  Above it: whole on 1
-# GPU, side on N GPUs (the exchange sits between a report's phases, so it needs two streams).
-PIPE_ALT_MAX_BYTES = 8 << 30
-
-TIMED_SPIN_CYCLES = 50_000  # ~20-25 us of device spin ahead of a timed report
-STAGGER_FRAC = 0.25  # PipelinedReports: a burst's second report starts this much of a phase later
-
-
-def _spin(cycles: int) -> None:
-    """A one-wave device spin on the current stream (torch's private _sleep kernel)."""
-    spin = getattr(torch.cuda, "_sleep", None)
-    if spin is not None:
-        spin(int(cycles))
-
-
-class PipelinedReports:
-    """Full reports as HIP graphs, two in flight.  Each report -- column-reference init,
-    statistics, scores + straggler masks -- ends with its packed results landing in one of two
-    pinned host buffers, so the host can read report i while report i+1 runs: the GPU sees
-    back-to-back reports instead of one report per host round trip.
-    mode "alt": report i runs on stream i % 2 with its own set of statistics / reference
-    buffers (_ReportBuffers; set 0 is the reporter's own), so report i+1's statistics kernel starts while report i's drains instead of
-    after it (the launch-to-launch transition of one stream); report i's scores wait for report
-    i-1's, so the individual history advances in submission order.  "side": every statistics
-    phase on one stream, every rest on another (buffer sets per report in flight as in alt).
-    "whole": one whole-report graph per report on the caller's stream (1 GPU).  "auto" (default):
-    alt for statistics phases up to PIPE_ALT_MAX_BYTES, else whole (side on N GPUs); on N GPUs
-    the choice takes the largest shard's bytes -- one all_reduce in the constructor, so every
-    rank constructs its PipelinedReports at the same point, as it calls report().  With two
-    streams the inputs a report reads must not change until it is collected (collect() orders
-    the caller's stream after it).  N GPUs (exchange): per report the statistics, the shard's
-    partials and the combine (+ result copy) are graphs and the all_gather of the partials is
-    issued eagerly between them, in report order on every rank (the gathered buffers are per
-    report in flight too).
-    timing: submit(timed=True) first lets the reports in flight finish, then replays the
-    statistics phase as its own graph between two timing events (ROCm's torch refuses events
-    inside a capture) and the rest of the report as another -- a clean measurement of the
-    statistics kernel on an otherwise idle device, for a sample of the reports.  timing_reps=n: that
-    graph holds the statistics phase n times back to back (same inputs and outputs each time) and
-    collect() returns the mean per phase, so the events' own overhead and a graph launch are spread
-    over n phases.
-    stats: the statistics phase as a callable stats(bufs) over a buffer set, or a list of them,
-    one per input set (report i runs stats[i % len(stats)]; MatrixReporter.pipelined and
-    pipelined_records build them).  stats_bytes: what one statistics phase reads (the mode
-    choice and the stagger).  inputs: per input set, the tensors its statistics phase
-    reads; collect() raises if one of them was modified in place by torch while the report was
-    in flight.
-    Other work on the same reporter (report(), a ReportGraph, compute_stats, reset_history)
-    issued before collect() is ordered after the reports in flight
-    (MatrixReporter._order_after_inflight)."""
-
-    def __init__(self, rep: MatrixReporter, stats, *, inputs, stats_bytes: int,
-                 timing: bool = False, mode: Optional[str] = None, depth: int = 2,
-                 timing_reps: int = 1):
-        self.mode = mode or _PIPE_MODE or "auto"
-        if callable(stats):
-            stats = [stats]
-        self.inputs = list(inputs)
-        if len(self.inputs) != len(stats) or depth % len(stats) != 0:
-            raise ValueError(f"pipelined reports: {len(stats)} input sets for depth {depth} "
-                             "(one inputs entry per set; the set count divides depth)")
-        if self.mode == "auto":
-            if rep.exchange and rep.world > 1:  # one mode on every rank (shards differ in size)
-                x = torch.tensor([float(stats_bytes)], dtype=torch.float64,
-                                 device="cpu" if rep.gloo else rep.device)
-                torch.distributed.all_reduce(x, torch.distributed.ReduceOp.MAX, group=rep.group)
-                stats_bytes = int(x.item())
-            self.mode = ("alt" if stats_bytes <= PIPE_ALT_MAX_BYTES else
-                         "side" if rep.exchange else "whole")
-        if self.mode not in ("alt", "side", "whole"):
-            raise ValueError(f"pipelined reports: mode {self.mode!r} (auto | alt | side | whole)")
-        if rep.exchange and self.mode == "whole":
-            raise RuntimeError("pipelined reports on N GPUs: two streams only (mode 'whole' is 1 GPU)")
-        self.alt = self.mode != "whole"  # two streams, a buffer set per report in flight
-        if depth < 2 or (depth > 2 and not self.alt):
-            raise ValueError("pipelined reports: depth >= 2 (> 2 with two streams only)")
-        self.depth = depth
-        self.rep, self.timing = rep, timing
-        if timing_reps < 1:
-            raise ValueError("timing_reps >= 1")
-        self.timing_reps = timing_reps
-        self.bufs = [torch.zeros_like(rep.h_out).pin_memory() for _ in range(depth)]
-
-        # the buffer set of each report in flight: with two streams one per report, the first the
-        # reporter's own; whole reports on one stream all use the reporter's own
-        self.slots = [rep.own] + [_ReportBuffers.new(rep) if self.alt else rep.own
-                                  for _ in range(depth - 1)]
-
-        def run_stats(k: int, reps: int = 1):
-            b = self.slots[k]
-            ready = b.clean
-            for _ in range(reps):
-                # a repeated phase reads the same inputs: the fused reference the previous one
-                # left is the same minimum, so it needs no re-initialisation either
-                b.clean = ready
-                stats[k % len(stats)](b)
-
-        def run_scores(k: int):
-            # the scores kernel writes the pinned buffer itself when its epilogue stores the
-            # error word (fused reference, R <= FUSED_REF_MAX_ROWS); otherwise the error word is
-            # zeroed on the device first and the results copied
-            if rep._fuse_ref():
-                rep.compute_scores(out_buf=self.bufs[k], bufs=self.slots[k])
-            else:
-                rep.compute_scores(bufs=self.slots[k])
-                rep._copy_out(self.bufs[k], self.slots[k])
-
-        if self.alt:
-            self.stats_g, self.rest_g, self.part_g, self.fin_g, self.stats_t = [], [], [], [], []
-            for k, b in enumerate(self.slots):
-                _warm_up(rep, stats[k % len(stats)], b)  # initialises this set's column reference too
-                ready = b.clean
-                self.stats_g.append(_capture(partial(run_stats, k)))
-                if timing:  # the timed statistics phase, timing_reps times in one graph,
-                    b.clean = ready  # replacing stats_g in a timed report
-                    self.stats_t.append(_capture(partial(run_stats, k, self.timing_reps)))
-                if rep.exchange:  # N GPUs: partials | eager all_gather | combine + result copy
-                    self.part_g.append(_capture(partial(rep._scores_partials, b)))
-                    self.fin_g.append(_capture(partial(rep._finalize, b),
-                                               partial(rep._copy_out, self.bufs[k], b)))
-                else:
-                    self.rest_g.append(_capture(partial(run_scores, k)))
-            self._needs_clean = rep.own.clean
-            self.streams = [torch.cuda.Stream(rep.device) for _ in range(depth)]
-            self.hist_done = [torch.cuda.Event() for _ in range(depth)]
-            self.stats_done = [torch.cuda.Event() for _ in range(depth)]
-        else:
-            _warm_up(rep, stats[0])
-            self._needs_clean = rep.own.clean  # as ReportGraph: every graph here pairs both phases
-            self.full = [_capture(partial(run_stats, k), partial(run_scores, k)) for k in range(2)]
-            if timing:
-                self.stats = _capture(partial(run_stats, 0, self.timing_reps))
-                self.rest = [_capture(partial(run_scores, k)) for k in range(2)]
-        if timing:
-            self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        # blocking-sync events: wait_event's fallback sleeps instead of polling
-        self.done = [torch.cuda.Event(blocking=True) for _ in range(depth)]
-        self._versions = [None] * depth  # the inputs' version counters at each slot's submit
-        # the one-time stagger of a burst's second report: a quarter of the statistics phase at
-        # ~6.5 TB/s (STAGGER_FRAC; NVRX_PIPE_STAGGER=0 disables), in spin cycles of ~2.2 GHz
-        frac = float(os.environ.get("NVRX_PIPE_STAGGER", STAGGER_FRAC))
-        self.stagger_cycles = int(frac * stats_bytes / 6.5e12 * 2.2e9) if stats_bytes else 0
-        self._burst = -2
-        self.pending = []  # (slot, statistics phases timed or 0) in flight, oldest first
-        self.ready = []    # results collected early (a timed submit drains), oldest first
-        self.n = 0
-        self.last_input = None
-        rep._pipes.add(self)
-
-    def submit(self, timed: bool = False) -> None:
-        """Queue the next report (at most `depth` in flight: collect() the oldest first)."""
-        if len(self.pending) == self.depth:
-            raise RuntimeError(f"{self.depth} reports in flight: collect() one first")
-        if self._needs_clean and not self.rep.own.clean:
-            raise RuntimeError("PipelinedReports: an unpaired statistics phase (ReportGraph."
-                               "run_stats without run_rest) left the column reference in use")
-        if timed and not self.timing:
-            raise RuntimeError("PipelinedReports(timing=True) is needed for timed reports")
-        k = self.n % self.depth
-        if timed:
-            while self.pending:  # the device idles before the measured statistics phase
-                self.ready.append(self._land())
-        self.rep._order_after_inflight(exclude=self)  # another pipeline's reports on this reporter
-        self._versions[k] = [t._version for t in self.inputs[k % len(self.inputs)]]
-        if timed:
-            # a short spin keeps the device busy while the host queues the graphs, so the
-            # first event fires right before the statistics phase rather than a graph-launch
-            # latency ahead of it
-            _spin(TIMED_SPIN_CYCLES)
-        if self.alt:
-            self._submit_two_streams(k, timed)
-        else:
-            self._submit_whole(k, timed)
-        self.rep.own.clean = self.rep._fuse_ref()
-        if not self.pending:
-            self._burst = self.n  # the first report of a burst (submitted to an empty pipeline)
-        self.pending.append((k, self.timing_reps if timed else 0))
-        self.n += 1
-
-    def _submit_two_streams(self, k: int, timed: bool) -> None:
-        # alt: report i on stream i % 2; side: every statistics phase on stream 0, every rest
-        # on stream 1 (slot k's previous report has finished with its buffers: done[k])
-        s = self.streams[k] if self.mode == "alt" else self.streams[0]
-        # the caller's work so far (inputs; the wait for the collected reports) comes first
-        s.wait_stream(torch.cuda.current_stream(self.rep.device))
-        s.wait_event(self.done[k])
-        if self.mode == "alt" and self.depth > 2:
-            # at most two statistics phases at once: report i's starts on the device as soon
-            # as report i-2's has finished, with no host round trip in between
-            s.wait_event(self.stats_done[(k - 2) % self.depth])
-        if (self.mode == "alt" and self.stagger_cycles > 0 and len(self.pending) == 1
-                and self.n == self._burst + 1):
-            # the second report of a burst (the pipeline was empty when the first was
-            # submitted) starts a quarter of a statistics phase after the first: staggered,
-            # one report's statistics kernel covers the other's end, scores and the host's
-            # next submission; started together, the two stay locked and the device idles at
-            # every pair's end (DESIGN 6)
-            with torch.cuda.stream(s):
-                _spin(self.stagger_cycles)
-        with torch.cuda.stream(s):
-            if timed:
-                self.ev[0].record(s)
-            (self.stats_t[k] if timed else self.stats_g[k]).replay()
-            if timed:
-                self.ev[1].record(s)
-        self.stats_done[k].record(s)
-        if self.mode == "side":
-            s = self.streams[1]
-            s.wait_event(self.stats_done[k])
-        with torch.cuda.stream(s):
-            s.wait_event(self.hist_done[(k - 1) % self.depth])  # report i-1's history update first
-            if self.rep.exchange:
-                self.part_g[k].replay()
-                self.hist_done[k].record(s)
-                # the eager all_gather of this slot's partials, ordered after them on s (every
-                # rank submits its reports, hence its collectives, in the same order)
-                self.rep._exchange(self.slots[k])
-                self.fin_g[k].replay()
-            else:
-                self.rest_g[k].replay()
-                self.hist_done[k].record(s)
-        self.done[k].record(s)
-
-    def _submit_whole(self, k: int, timed: bool) -> None:
-        if timed:
-            self.ev[0].record()
-            self.stats.replay()
-            self.ev[1].record()
-            self.rest[k].replay()
-        else:
-            self.full[k].replay()
-        self.done[k].record()
-
-    def _land(self):
-        k, timed = self.pending.pop(0)  # timed: the timed statistics phases (0: untimed)
-        ev = self.done[k]
-        wait_event(ev)
-        if self.alt:  # the caller's later work (new inputs, the history) follows this report
-            torch.cuda.current_stream(self.rep.device).wait_event(ev)
-        self.last_input = k % len(self.inputs)  # the input set the collected report read
-        now = [t._version for t in self.inputs[k % len(self.inputs)]]
-        if now != self._versions[k]:
-            raise RuntimeError("PipelinedReports: an input of this report was modified in place "
-                               "while the report was in flight (submit() -> collect()); its "
-                               "results are undefined -- modify inputs only after collect()")
-        ms = self.ev[0].elapsed_time(self.ev[1]) / timed if timed else None
-        return self.slots[k].unpack(self.bufs[k]), ms
-
-    def collect(self):
-        """(BatchResult, statistics ms for a timed report or None) of the oldest report, once it
-        landed."""
-        if self.ready:
-            return self.ready.pop(0)
-        return self._land()

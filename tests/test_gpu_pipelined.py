@@ -350,6 +350,29 @@ def test_distinct_inputs_per_report_in_flight(mode):
         b.pipelined(src + [src[0]], S, mode=mode)
 
 
+@pytest.mark.parametrize("mode", ["alt", "side", "whole"])
+def test_timed_reports_read_their_own_input(mode):
+    """a timed report replays its own slot's statistics graph, so with two
+    input sets timed report i reads x[i % 2] in every mode ("whole" once held one timed
+    statistics graph, over input 0, for both slots)."""
+    R, K, S, cap = 8, 32, 600, 512
+    # (the generator hashes seed ^ sample index: seeds that differ only in bits below R*K*S
+    # permute the same samples, here within the retained windows -- identical statistics)
+    src = [synth.synth_matrix(R, K, S, seed=seed, device="cuda") for seed in (70, 71 << 20)]
+    a = batch.MatrixReporter(R, K, cap=cap, thr_rel=0.8, thr_ind=0.8)
+    b = batch.MatrixReporter(R, K, cap=cap, thr_rel=0.8, thr_ind=0.8)
+    want = [a.report(src[i % 2], S) for i in range(6)]
+    assert not np.array_equal(want[0].gpu_relative, want[1].gpu_relative)  # the inputs do differ
+    pipe = b.pipelined(src, S, mode=mode, timing=True, timing_reps=2)
+    for i, w in enumerate(want):
+        pipe.submit(timed=True)
+        res, ms = pipe.collect()
+        assert isinstance(ms, float) and ms > 0.0, (i, ms)
+        assert pipe.last_input == i % 2
+        assert res.err == w.err, i
+        _same(w, res)
+
+
 def test_input_modified_in_flight_is_refused():
     """An input changed by a torch in-place op between submit() and collect() is reported
     (the version counter of the tensor moved); changes between reports are fine."""
