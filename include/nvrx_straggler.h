@@ -29,7 +29,8 @@
  *                          start, stop, get_stats, reset)                                 cupti_src/cupti_module_py.cpp:33-54
  *   nvrx_records_*         CuptiProfiler::bufferCompleted record loop + CircularBuffer     cupti_src/CuptiProfiler.cpp:168-203, CircularBuffer.h:53-69
  * Beyond the reference (no counterpart there): nvrx_segment_quantiles_*, nvrx_score_attribution,
- * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms.
+ * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms,
+ * nvrx_histogram_sum / _tail_threshold / _tail_scores.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -219,6 +220,73 @@ int nvrx_segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off,
                                   const int32_t* seg_len, int64_t nseg, int64_t max_len,
                                   int64_t cap, int32_t aligned16, int32_t accumulate,
                                   uint32_t* counts, int32_t* num, void* stream);
+
+/* Tail scores from the histograms: one score per row (rank) on the scale of the GPU scores -- about
+ * 1 for a healthy rank, lower for a straggler -- that sees what the median hides: a rank slow on
+ * every n-th call.  No reference counterpart.  Computed from integer counts, so exact and
+ * deterministic.  The definition is part of the ABI; every sum is an exact integer.
+ * Inputs: counts C[r][k][b], u32 over the NVRX_HIST_BINS fixed buckets, R rows x K kernels;
+ * permille pm, an integer in [0, 1000].
+ *   1. fleet histogram   F[k][b] = sum_r C[r][k][b]                                        (u64)
+ *   2. threshold bucket  N_k = sum_b F[k][b];  T_k = the bucket that holds the fleet's sample of
+ *                        0-based rank (pm * (N_k - 1)) / 1000 (64-bit integer division; the product
+ *                        is taken exactly), i.e. the smallest b with sum_{b' <= b} F[k][b'] > rank:
+ *                        the rank rule of the quantile calls.  T_k = -1 when N_k == 0 or
+ *                        col_valid[k] == 0; such a kernel is skipped everywhere below.
+ *   3. weights           w(b) = nvrx_histogram_edge(min(b, 238)) (u64): the bucket's lower edge in ns.
+ *                        Buckets 238 and 239 both weigh NVRX_KEY_WIDE: keys there are not ns, and
+ *                        3.76 s is still a true lower bound.
+ *   4. per row           total_ns[r] = sum_k sum_b         C[r][k][b] * w(b)
+ *                        tail_ns[r]  = sum_k sum_{b > T_k} C[r][k][b] * w(b)
+ *                        (u64, over the kernels with T >= 0; lower bounds of real time, so they do
+ *                        not overflow in a real run, and wrap mod 2^64 otherwise);
+ *                        tail_calls[r][k] = sum_{b > T_k} C[r][k][b] (u32; 0 for a skipped kernel)
+ *   5. fleet             fleet_total = sum_k sum_b F[k][b] * w(b),  fleet_tail = the same over
+ *                        b > T_k, over the kernels with T >= 0
+ *   6. score             in f64, each operation rounded separately, each u64 converted to f64
+ *                        (round to nearest even) first:
+ *                            share_r  = tail_ns[r] / total_ns[r]
+ *                            fs       = fleet_tail / fleet_total
+ *                            score[r] = (1.0 - share_r) / (1.0 - fs)
+ *                        NaN when total_ns[r] == 0, fleet_total == 0 or 1.0 - fs == 0.0;
+ *                        strag[r] = score[r] < score_thr (strict; NaN never), as nvrx_stragglers.
+ * score is about the time the row would have needed with a fleet-typical tail, divided by the time
+ * it needed -- the meaning of ref / MED.  Limits: a slowdown of less than one bucket (12.5 %) may
+ * not cross T_k; and pm must leave more room than the slow rank's own share of the fleet's samples
+ * (8 ranks, one of them slow on every 10th call: its slow calls are 1.25 % of the fleet, pm = 990
+ * puts T_k inside them -- use 950 there).
+ *
+ * nvrx_histogram_sum: fleet[K][240] (u64, 16-byte aligned) = the column sum of counts[R][K][240]
+ *   (u32, 16-byte aligned, rows contiguous); accumulate != 0 adds to what fleet holds (a run-long
+ *   fleet), otherwise all K * 240 bins are written.
+ * nvrx_histogram_tail_threshold: thr[K] (i32) = T_k of fleet for `permille`; col_valid: [K] u8 or
+ *   NULL (all valid); fleet_sums[2] (u64) = {fleet_tail, fleet_total}, written in full.
+ * nvrx_histogram_tail_scores: steps 4 and 6 for the R rows of counts.  Column k uses
+ *   thr[thr_index ? thr_index[k] : k]; a negative index, like a negative thr, skips the kernel (a
+ *   rank whose kernels are a subset of the fleet's, as ref_index of nvrx_scores).  tail_calls and
+ *   strag may be NULL.
+ * K * 240 and R * K must be below 2^31.  R == 0 or K == 0 launches nothing (outputs untouched).
+ * Stream-ordered: kernels on `stream` only, no allocation, no synchronisation, no host read-back;
+ * the three calls in a row form a linear sequence that can be captured in a graph. */
+typedef struct nvrx_tail_args {
+    int64_t R, K;
+    const uint32_t* counts;     /* [R][K][NVRX_HIST_BINS] */
+    const int32_t* thr;         /* threshold buckets, from nvrx_histogram_tail_threshold */
+    const int32_t* thr_index;   /* [K] or NULL */
+    const uint64_t* fleet_sums; /* [2] {fleet_tail, fleet_total} */
+    uint64_t* tail_ns;          /* [R] */
+    uint64_t* total_ns;         /* [R] */
+    double* score;              /* [R] */
+    uint32_t* tail_calls;       /* [R][K] or NULL */
+    uint8_t* strag;             /* [R] or NULL */
+    double score_thr;
+} nvrx_tail_args;
+int nvrx_histogram_sum(const uint32_t* counts, int64_t R, int64_t K, int32_t accumulate,
+                       uint64_t* fleet, void* stream);
+int nvrx_histogram_tail_threshold(const uint64_t* fleet, int64_t K, int32_t permille,
+                                  const uint8_t* col_valid, int32_t* thr, uint64_t* fleet_sums,
+                                  void* stream);
+int nvrx_histogram_tail_scores(const nvrx_tail_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

@@ -4,7 +4,8 @@
 // Thin host glue: argument/shape checks on the host before any launch, HIP error -> status
 // code + thread-local message.  The profiler handle that replaces the reference's
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
-// kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip and records.hip.
+// kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
+// histogram_scores.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -86,6 +87,17 @@ int check_ragged(const char* entry, const uint32_t* ns, const int64_t* seg_off, 
     NVRX_CHECK_ARG(nseg == 0 || seg_off, fn + ": null seg_off");
     NVRX_CHECK_ARG(nseg == 0 || max_len == 0 || ns, fn + ": null ns");
     return check_retained(fn, "max_len", max_len, cap);
+}
+
+// R rows x K kernels of the three nvrx_histogram_* tail-score entries
+int check_tail_shape(const char* entry, int64_t R, int64_t K) {
+    const std::string fn(entry);
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
+    NVRX_CHECK_ARG(K >= 0, fn + ": negative K");
+    NVRX_CHECK_ARG(K <= lim / NVRX_HIST_BINS, fn + ": K * 240 must be below 2^31");
+    NVRX_CHECK_ARG(R == 0 || K <= lim / R, fn + ": R * K must be below 2^31");
+    return NVRX_OK;
 }
 
 bool all_columns(const nvrx_stats_soa* out) {
@@ -233,6 +245,56 @@ int nvrx_segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off,
                                                      aligned16 != 0, accumulate != 0, counts, num,
                                                      S(stream)),
                       "nvrx_segment_histogram_ragged");
+}
+
+// ------------------------------------------------------------------ tail scores
+int nvrx_histogram_sum(const uint32_t* counts, int64_t R, int64_t K, int32_t accumulate,
+                       uint64_t* fleet, void* stream) {
+    if (int rc = check_tail_shape("nvrx_histogram_sum", R, K)) return rc;
+    if (R > 0 && K > 0) {
+        NVRX_CHECK_ARG(counts, "nvrx_histogram_sum: null counts");
+        NVRX_CHECK_ARG(fleet, "nvrx_histogram_sum: null fleet");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)counts & 15) == 0, "nvrx_histogram_sum: counts not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)fleet & 15) == 0, "nvrx_histogram_sum: fleet not 16-byte aligned");
+    return hip_status(nvrx::histogram_sum(counts, R, K, accumulate != 0, fleet, S(stream)),
+                      "nvrx_histogram_sum");
+}
+
+int nvrx_histogram_tail_threshold(const uint64_t* fleet, int64_t K, int32_t permille,
+                                  const uint8_t* col_valid, int32_t* thr, uint64_t* fleet_sums,
+                                  void* stream) {
+    if (int rc = check_tail_shape("nvrx_histogram_tail_threshold", 0, K)) return rc;
+    NVRX_CHECK_ARG(permille >= 0 && permille <= 1000,
+                   "nvrx_histogram_tail_threshold: permille outside [0, 1000]");
+    if (K > 0) {
+        NVRX_CHECK_ARG(fleet, "nvrx_histogram_tail_threshold: null fleet");
+        NVRX_CHECK_ARG(thr, "nvrx_histogram_tail_threshold: null thr");
+        NVRX_CHECK_ARG(fleet_sums, "nvrx_histogram_tail_threshold: null fleet_sums");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)fleet & 15) == 0,
+                   "nvrx_histogram_tail_threshold: fleet not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)fleet_sums & 7) == 0,
+                   "nvrx_histogram_tail_threshold: fleet_sums not 8-byte aligned");
+    return hip_status(nvrx::histogram_tail_threshold(fleet, K, permille, col_valid, thr, fleet_sums,
+                                                     S(stream)),
+                      "nvrx_histogram_tail_threshold");
+}
+
+int nvrx_histogram_tail_scores(const nvrx_tail_args* a, void* stream) {
+    NVRX_CHECK_ARG(a, "nvrx_histogram_tail_scores: null args");
+    if (int rc = check_tail_shape("nvrx_histogram_tail_scores", a->R, a->K)) return rc;
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->counts, "nvrx_histogram_tail_scores: null counts");
+        NVRX_CHECK_ARG(a->thr, "nvrx_histogram_tail_scores: null thr");
+        NVRX_CHECK_ARG(a->fleet_sums, "nvrx_histogram_tail_scores: null fleet_sums");
+        NVRX_CHECK_ARG(a->tail_ns, "nvrx_histogram_tail_scores: null tail_ns");
+        NVRX_CHECK_ARG(a->total_ns, "nvrx_histogram_tail_scores: null total_ns");
+        NVRX_CHECK_ARG(a->score, "nvrx_histogram_tail_scores: null score");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0,
+                   "nvrx_histogram_tail_scores: counts not 16-byte aligned");
+    return hip_status(nvrx::histogram_tail_scores(*a, S(stream)), "nvrx_histogram_tail_scores");
 }
 
 // ------------------------------------------------------------------ scoring

@@ -38,6 +38,14 @@ hipError_t segment_histogram_ragged(const uint32_t* ns, const int64_t* seg_off, 
                                     int64_t nseg, int64_t max_len, int64_t cap, bool aligned16,
                                     int accumulate, uint32_t* counts, int32_t* num, hipStream_t st);
 
+// tail scores from the histograms (histogram_scores.hip): fleet [K][240] u64, thr [K], fleet_sums [2]
+hipError_t histogram_sum(const uint32_t* counts, int64_t R, int64_t K, int accumulate, uint64_t* fleet,
+                         hipStream_t st);
+hipError_t histogram_tail_threshold(const uint64_t* fleet, int64_t K, int permille,
+                                    const uint8_t* col_valid, int32_t* thr, uint64_t* fleet_sums,
+                                    hipStream_t st);
+hipError_t histogram_tail_scores(const nvrx_tail_args& a, hipStream_t st);
+
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 
 // kernel_ref puts NVRX_KREF_ROWS rows on each block of grid.y (at most 65535 blocks): the

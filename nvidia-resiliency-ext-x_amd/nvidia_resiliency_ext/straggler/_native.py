@@ -68,6 +68,14 @@ class AttributionArgs(ctypes.Structure):
     ]
 
 
+class TailArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("counts", P), ("thr", P), ("thr_index", P), ("fleet_sums", P),
+        ("tail_ns", P), ("total_ns", P), ("score", P), ("tail_calls", P), ("strag", P),
+        ("score_thr", f64),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -109,6 +117,9 @@ SIGNATURES = {
     "nvrx_histogram_edge": (ctypes.c_uint64, [i32]),
     "nvrx_segment_histogram_strided": (ctypes.c_int, [P, i64, i64, i64, i64, i64, i32, P, P, P]),
     "nvrx_segment_histogram_ragged": (ctypes.c_int, [P, P, P, i64, i64, i64, i32, i32, P, P, P]),
+    "nvrx_histogram_sum": (ctypes.c_int, [P, i64, i64, i32, P, P]),
+    "nvrx_histogram_tail_threshold": (ctypes.c_int, [P, i64, i32, P, P, P, P]),
+    "nvrx_histogram_tail_scores": (ctypes.c_int, [ctypes.POINTER(TailArgs), P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

@@ -67,6 +67,18 @@ class BatchAttribution:
     err: int = 0          # 1: some scored MED was 0 (that kernel is left out)
 
 
+@dataclass
+class BatchTailScores:
+    """MatrixReporter.tail_scores: per rank a score from the tails of the fleet's histograms."""
+    score: np.ndarray             # [R] f64, about 1 healthy, lower = more time in the tail; NaN: no samples
+    tail_ns: np.ndarray           # [R] u64 weighted counts above the threshold buckets (ns, lower bound)
+    total_ns: np.ndarray          # [R] u64 all weighted counts
+    fleet_share: float            # fleet_tail / fleet_total: the tail's share of the fleet's time
+    stragglers: np.ndarray        # [R] bool, score < threshold (NaN never)
+    threshold_bucket: np.ndarray  # [K] i32 bucket T_k of the fleet's quantile (-1: kernel skipped)
+    tail_calls: Optional[torch.Tensor] = None  # [R, K] int32 on the device, on request
+
+
 @dataclass(eq=False)
 class _ReportBuffers:
     """The device buffers of one report: segment statistics, the per-kernel reference the
@@ -172,6 +184,7 @@ class MatrixReporter:
         self._pipes = weakref.WeakSet()  # PipelinedReports over this reporter
         self._attr_ref = None  # attribute(): its own column reference and packed outputs per top
         self._attr_out = {}
+        self._tail = None  # tail_scores(): fleet histogram and packed outputs, allocated at first use
 
     @property
     def stats(self) -> ops.SegmentStats:
@@ -329,8 +342,8 @@ class MatrixReporter:
         windows (the last ``cap`` of ``s_push`` samples per rank and kernel): an int32 device
         tensor [R, K, 240] over the fixed buckets of ``straggler.histograms``.  ``out``: the
         tensor to write, or with ``accumulate=True`` to add this interval's counts to.  The
-        buckets are shared, so ``out.sum(0, dtype=torch.int64)`` is the world's histogram per
-        kernel.  It reads ``ns`` only and changes none of the report's buffers; the call queues
+        buckets are shared, so the sum over ranks (``ops.histogram_sum``) is the world's histogram
+        per kernel, and ``tail_scores`` turns the counts into a score per rank.  It reads ``ns`` only and changes none of the report's buffers; the call queues
         behind reports still in flight.  Beyond the reference."""
         self._order_after_inflight()
         R, K = self.R, self.K
@@ -338,6 +351,64 @@ class MatrixReporter:
         c = ops.segment_histogram_strided(ns.view(-1), R * K, s_push, 0, s_push, cap=self.cap,
                                           out=flat, accumulate=accumulate)
         return c.view(R, K, histograms.BINS)
+
+    def tail_scores(self, counts: torch.Tensor, permille: int = 990,
+                    threshold: Optional[float] = None, tail_calls: bool = False) -> BatchTailScores:
+        """A tail score per rank from the histograms ``histograms()`` returned (int32 device
+        tensor [R, K, 240], possibly accumulated over reports): what the median-based scores
+        cannot see, a rank that is slow on every n-th call.  The fleet is the sum over ranks, T_k
+        the bucket of its ``permille`` quantile per kernel (kernels filtered by ``col_valid`` or
+        without samples are skipped), ``w(b)`` a bucket's lower edge in ns, and
+
+            score[r] = (1 - tail_ns[r] / total_ns[r]) / (1 - fleet_tail / fleet_total)
+
+        with ``tail_ns`` the rank's weighted counts above T_k: about 1 for a healthy rank, lower
+        for one that spends more of its time in the fleet's tail, on the scale of the GPU scores;
+        ``stragglers`` is ``score < threshold`` (None: the reporter's relative threshold).  Exact
+        integer sums on the device (include/nvrx_straggler.h).  A slowdown below one bucket
+        (12.5 %) may not cross T_k, and ``permille`` must leave more room than the slow rank's own
+        share of the fleet's samples (8 ranks, every 10th call slow: use 950, not 990).
+        ``tail_calls=True`` also returns, on the device, the int32 [R, K] calls above T_k.  It
+        queues behind reports in flight and changes none of the report's buffers; its own buffers
+        are allocated once per reporter, and the results come in one device-to-host copy.  Beyond
+        the reference."""
+        pm = ops.tail_permille(permille)
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.tail_scores: tail scores across kernel "
+                                      "shards (exchange=True) are not supported")
+        R, K, d = self.R, self.K, self.device
+        if tuple(counts.shape) != (R, K, histograms.BINS):
+            raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
+        self._order_after_inflight()
+        if self._tail is None:
+            # packed: [score f64 R][tail_ns i64 R][total_ns i64 R][fleet_sums i64 2][thr i32 K+pad][strag u8 R]
+            kp = (K + 1) // 2 * 2
+            self._tail = dict(buf=torch.zeros(8 * (3 * R + 2) + 4 * kp + R, dtype=torch.uint8, device=d),
+                              fleet=torch.empty((K, histograms.BINS), dtype=torch.int64, device=d),
+                              calls=None, kp=kp)
+        t = self._tail
+        kp, buf = t["kp"], t["buf"]
+        i64 = buf[:8 * (3 * R + 2)].view(torch.int64)
+        thr = buf[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(torch.int32)[:K]
+        sums = i64[3 * R:]
+        out = ops.TailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
+                             buf[8 * (3 * R + 2) + 4 * kp:])
+        if tail_calls and t["calls"] is None:
+            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
+        ops.histogram_sum(counts, out=t["fleet"])
+        ops.histogram_tail_threshold(t["fleet"], pm, col_valid=self.col_valid, thr=thr, fleet_sums=sums)
+        res = ops.histogram_tail_scores(counts, thr, sums, out=out,
+                                        score_thr=self.thr_rel if threshold is None else threshold,
+                                        tail_calls=t["calls"] if tail_calls else False)
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        h64 = host[:8 * (3 * R + 2)].view(np.uint64)
+        ftail, ftotal = int(h64[3 * R]), int(h64[3 * R + 1])
+        return BatchTailScores(h64[:R].view(np.float64).copy(), h64[R:2 * R].copy(),
+                               h64[2 * R:3 * R].copy(),
+                               float(ftail) / float(ftotal) if ftotal else float("nan"),
+                               host[8 * (3 * R + 2) + 4 * kp:].astype(bool),
+                               host[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(np.int32)[:K].copy(),
+                               res.tail_calls)
 
     def attribute(self, top: int = 8, kind: str = "relative") -> BatchAttribution:
         """Which kernels made each rank's score what it is: per rank the `top` (1..16) kernels

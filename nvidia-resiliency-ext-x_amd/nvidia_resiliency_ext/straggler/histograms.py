@@ -14,8 +14,14 @@ and ``MatrixReporter.histograms`` count duration keys (``_native.duration_keys``
 The edges are the same for every kernel, rank and report (they are part of the C ABI), so
 counts add: ``merge`` over ranks gives the fleet-wide distribution of a kernel, over reports a
 whole run's, and ``quantile_bounds`` brackets any quantile of the merged samples by one bucket.
+``tail_threshold`` and ``tail_scores`` are the host twins (Python-integer sums) of the device's
+tail scores (``ops.histogram_sum`` / ``histogram_tail_threshold`` / ``histogram_tail_scores``,
+``MatrixReporter.tail_scores``, ``Detector.kernel_tail_score``): a per-rank score from the fleet's
+summed histograms that sees a rank slow on every n-th call, which its median hides.
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -74,13 +80,108 @@ def merge(*counts) -> np.ndarray:
     return total
 
 
+def _check_permille(permille) -> int:
+    if isinstance(permille, bool) or int(permille) != permille or not 0 <= permille <= 1000:
+        raise ValueError(f"permille must be an int in [0, 1000], got {permille!r}")
+    return int(permille)
+
+
+def weights() -> list:
+    """w(b) of the tail scores as Python ints: the lower edge of bucket min(b, 238) in ns (the
+    two wide buckets both weigh ``KEY_WIDE``, a true lower bound of their durations)."""
+    e = edges_keys().tolist()
+    return [e[min(b, BINS - 2)] for b in range(BINS)]
+
+
+def tail_threshold(fleet, permille: int) -> np.ndarray:
+    """Threshold bucket per kernel of a fleet histogram ``fleet`` ([K, 240] counts, e.g.
+    ``merge`` over the ranks): int64 [K], the bucket that holds the fleet's sample of 0-based rank
+    ``(permille * (N - 1)) // 1000`` (the rank rule of the quantile calls, the bucket
+    ``quantile_bounds`` brackets); -1 for a kernel without samples.  Python-integer sums: the
+    host twin of ``ops.histogram_tail_threshold``."""
+    pm = _check_permille(permille)
+    f = merge(fleet) if np.asarray(fleet).dtype != np.uint64 else np.asarray(fleet)
+    if f.ndim != 2 or f.shape[1] != BINS:
+        raise ValueError(f"fleet must have shape [K, {BINS}]")
+    out = np.full(f.shape[0], -1, np.int64)
+    for k, row in enumerate(f.tolist()):
+        n = sum(row)
+        if n == 0:
+            continue
+        rank, c = (pm * (n - 1)) // 1000, 0
+        for b, v in enumerate(row):
+            c += v
+            if c > rank:
+                out[k] = b
+                break
+    return out
+
+
+@dataclass
+class TailScores:
+    """``tail_scores``: per row the tail score and what it was made from."""
+    score: np.ndarray             # [R] f64, NaN without weighted samples
+    tail_ns: np.ndarray           # [R] u64, time above the fleet's threshold buckets (lower bound)
+    total_ns: np.ndarray          # [R] u64
+    fleet_share: float            # fleet_tail / fleet_total (NaN for an empty fleet)
+    threshold_bucket: np.ndarray  # [K] i64, -1: kernel skipped
+    tail_calls: np.ndarray        # [R, K] i64 calls above the threshold bucket
+    fleet_tail: int = 0
+    fleet_total: int = 0
+
+
+def tail_scores(counts, permille: int, col_valid=None) -> TailScores:
+    """Tail score per row of ``counts`` ([R, K, 240]; device counts as int32 are read as u32),
+    the host twin of ``ops.histogram_sum`` -> ``histogram_tail_threshold`` ->
+    ``histogram_tail_scores`` with the same definition (include/nvrx_straggler.h): the fleet is
+    the sum over rows, T_k its threshold bucket at ``permille`` (kernels with ``col_valid[k] ==
+    0`` or no sample are skipped), ``w(b)`` the bucket's lower edge in ns,
+
+        score[r] = (1 - tail_ns[r] / total_ns[r]) / (1 - fleet_tail / fleet_total)
+
+    with ``tail_ns`` the weighted counts above T_k.  About 1 for a healthy row, lower for one whose
+    time sits in the fleet's tail; exact integer sums (Python ints, wrapped to 64 bits like the
+    device's), three f64 operations.  A slowdown below one bucket (12.5 %) may not cross T_k, and
+    ``permille`` must leave more room than the slow row's own share of the fleet's samples."""
+    pm = _check_permille(permille)
+    c = merge(counts)
+    if c.ndim != 3 or c.shape[2] != BINS:
+        raise ValueError(f"counts must have shape [R, K, {BINS}]")
+    R, K, _ = c.shape
+    T = tail_threshold(c.sum(0), pm) if R else np.full(K, -1, np.int64)
+    if col_valid is not None:
+        T = np.where(np.asarray(col_valid).astype(bool), T, -1)
+    w, M = weights(), (1 << 64) - 1
+    rows = c.tolist()
+    tail, total = [0] * R, [0] * R
+    calls = np.zeros((R, K), np.int64)
+    for k in range(K):
+        t = int(T[k])
+        if t < 0:
+            continue
+        for r in range(R):
+            h = rows[r][k]
+            total[r] += sum(v * w[b] for b, v in enumerate(h) if v)
+            tail[r] += sum(h[b] * w[b] for b in range(t + 1, BINS) if h[b])
+            calls[r, k] = sum(h[t + 1:]) & 0xFFFFFFFF
+    ftail, ftotal = sum(tail) & M, sum(total) & M
+    tail, total = [v & M for v in tail], [v & M for v in total]
+    nan = float("nan")
+    fs = float(ftail) / float(ftotal) if ftotal else nan
+    den = 1.0 - fs
+    score = [(1.0 - float(tl) / float(tt)) / den if tt and ftotal and den != 0.0 else nan
+             for tl, tt in zip(tail, total)]
+    return TailScores(np.asarray(score, np.float64).reshape(R), np.asarray(tail, np.uint64).reshape(R),
+                      np.asarray(total, np.uint64).reshape(R), fs, T.astype(np.int64), calls,
+                      ftail, ftotal)
+
+
 def quantile_bounds(counts, permille: int):
     """``(lo_us, hi_us)`` of the bucket that holds the quantile ``permille`` (an int in
     [0, 1000]) of the n samples counted in ``counts`` ([240]): the sample of 0-based rank
     ``(permille * (n - 1)) // 1000``, the rank rule of the quantile calls, lies in
     ``[lo_us, hi_us)`` (``hi_us`` is +inf for the last bucket).  (NaN, NaN) for n = 0."""
-    if isinstance(permille, bool) or int(permille) != permille or not 0 <= permille <= 1000:
-        raise ValueError(f"permille must be an int in [0, 1000], got {permille!r}")
+    _check_permille(permille)
     c = merge(counts)
     if c.shape != (BINS,):
         raise ValueError(f"counts must have shape [{BINS}]")

@@ -240,6 +240,139 @@ def segment_histogram_ragged(ns: torch.Tensor, seg_off: torch.Tensor, seg_len: O
     return out
 
 
+def _tail_counts(counts):
+    """counts of the tail-score calls: a contiguous, 16-byte aligned int32 device tensor
+    [R, K, 240] (u32 counts, as the histogram calls write them); returns (R, K)."""
+    N.require_device(counts, "counts")
+    if (counts.dtype not in (torch.int32, torch.uint32) or counts.dim() != 3 or
+            counts.shape[2] != N.HIST_BINS or not counts.is_contiguous() or counts.data_ptr() % 16):
+        raise ValueError("counts must be a contiguous, 16-byte aligned int32 tensor of shape [R, K, 240]")
+    return counts.shape[0], counts.shape[1]
+
+
+def _tail_tensor(t, name, dtype, shape):
+    N.require_device(t, name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}")
+    return t
+
+
+def tail_permille(permille) -> int:
+    """The one permille of the tail-score calls: an int in [0, 1000]; ValueError if not."""
+    if isinstance(permille, bool) or not isinstance(permille, numbers.Integral) or \
+            not 0 <= permille <= 1000:
+        raise ValueError(f"permille must be an int in [0, 1000], got {permille!r}")
+    return int(permille)
+
+
+def histogram_sum(counts: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  accumulate: bool = False, stream=None) -> torch.Tensor:
+    """The fleet histogram: the sum over the R rows of ``counts`` ([R, K, 240] int32 holding u32
+    counts) as an int64 [K, 240] tensor (u64 on the device), exact.  ``out``: the tensor to write,
+    or with ``accumulate=True`` to add to (then required) -- a run-long fleet.  What
+    ``counts.sum(0, dtype=torch.int64)`` computes, in one pass of 16-byte loads with the rows
+    split over the grid."""
+    _histogram_request(out, accumulate)
+    R, K = _tail_counts(counts)
+    if out is None:
+        out = torch.empty((K, N.HIST_BINS), dtype=torch.int64, device=counts.device)
+    _tail_tensor(out, "out", torch.int64, (K, N.HIST_BINS))
+    if R == 0 and not accumulate:
+        out.zero_()  # the sum of no rows (the C call launches nothing)
+    N.call("nvrx_histogram_sum", counts.data_ptr(), R, K, int(bool(accumulate)), out.data_ptr(),
+           _stream(stream))
+    return out
+
+
+def histogram_tail_threshold(fleet: torch.Tensor, permille: int, col_valid=None,
+                             thr: Optional[torch.Tensor] = None,
+                             fleet_sums: Optional[torch.Tensor] = None, stream=None):
+    """Per kernel of a fleet histogram (int64 [K, 240]) the threshold bucket of the tail scores:
+    ``thr`` int32 [K], the bucket of the fleet's sample of 0-based rank ``(permille * (N - 1)) //
+    1000`` (-1: no samples, or ``col_valid[k] == 0``), and ``fleet_sums`` int64 [2] = the fleet's
+    weighted {tail, total} ns over the kernels taken.  Returns (thr, fleet_sums)."""
+    pm = tail_permille(permille)
+    N.require_device(fleet, "fleet")
+    if fleet.dim() != 2:
+        raise ValueError("fleet must be a contiguous int64 tensor of shape [K, 240]")
+    K = fleet.shape[0]
+    _tail_tensor(fleet, "fleet", torch.int64, (K, N.HIST_BINS))
+    if thr is None:
+        thr = torch.empty(K, dtype=torch.int32, device=fleet.device)
+    if fleet_sums is None:
+        fleet_sums = torch.zeros(2, dtype=torch.int64, device=fleet.device)
+    _tail_tensor(thr, "thr", torch.int32, (K,))
+    _tail_tensor(fleet_sums, "fleet_sums", torch.int64, (2,))
+    if col_valid is not None:
+        _tail_tensor(col_valid, "col_valid", col_valid.dtype, (K,))
+        if col_valid.element_size() != 1:
+            raise ValueError("col_valid must be a uint8 / bool tensor of shape [K]")
+    N.call("nvrx_histogram_tail_threshold", fleet.data_ptr(), K, pm, N.ptr(col_valid),
+           thr.data_ptr(), fleet_sums.data_ptr(), _stream(stream))
+    return thr, fleet_sums
+
+
+@dataclass
+class TailScores:
+    """Per row of ``histogram_tail_scores`` (device tensors): score [R] float64, tail_ns /
+    total_ns [R] int64 (u64 on the device), strag [R] uint8 (score < score_thr), tail_calls
+    [R, K] int32 (u32; None when not requested)."""
+
+    score: torch.Tensor
+    tail_ns: torch.Tensor
+    total_ns: torch.Tensor
+    strag: torch.Tensor
+    tail_calls: Optional[torch.Tensor] = None
+
+
+def histogram_tail_scores(counts: torch.Tensor, thr: torch.Tensor, fleet_sums: torch.Tensor, *,
+                          score_thr: float = 0.75, thr_index: Optional[torch.Tensor] = None,
+                          tail_calls=False, out: Optional[TailScores] = None,
+                          stream=None) -> TailScores:
+    """Tail score per row of ``counts`` ([R, K, 240]) against the threshold buckets ``thr`` and the
+    fleet's ``fleet_sums`` of ``histogram_tail_threshold``: ``score = (1 - tail_ns / total_ns) /
+    (1 - fleet_tail / fleet_total)`` with ``tail_ns`` the row's weighted counts above the threshold
+    buckets (NaN for a row without weighted samples; never flagged).  Column k uses
+    ``thr[thr_index[k]]`` when ``thr_index`` (int32 [K]) is given; a negative index skips the
+    kernel.  ``tail_calls=True`` (or an int32 [R, K] tensor) also counts, per row and kernel, the
+    calls above the threshold bucket.  ``out``: preallocated outputs."""
+    R, K = _tail_counts(counts)
+    d = counts.device
+    N.require_device(thr, "thr")
+    if thr.dtype != torch.int32 or thr.dim() != 1 or not thr.is_contiguous():
+        raise ValueError("thr must be a contiguous int32 tensor")
+    if thr_index is None:
+        if thr.numel() != K:
+            raise ValueError("thr must hold K entries (or pass thr_index)")
+    else:
+        _tail_tensor(thr_index, "thr_index", torch.int32, (K,))
+    _tail_tensor(fleet_sums, "fleet_sums", torch.int64, (2,))
+    if out is None:
+        out = TailScores(torch.empty(R, dtype=torch.float64, device=d),
+                         torch.empty(R, dtype=torch.int64, device=d),
+                         torch.empty(R, dtype=torch.int64, device=d),
+                         torch.empty(R, dtype=torch.uint8, device=d))
+    _tail_tensor(out.score, "out.score", torch.float64, (R,))
+    _tail_tensor(out.tail_ns, "out.tail_ns", torch.int64, (R,))
+    _tail_tensor(out.total_ns, "out.total_ns", torch.int64, (R,))
+    if out.strag is not None:
+        _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
+    calls = None
+    if tail_calls is True:
+        calls = out.tail_calls
+        if calls is None:
+            calls = torch.empty((R, K), dtype=torch.int32, device=d)
+    elif tail_calls is not False and tail_calls is not None:
+        calls = tail_calls
+    if calls is not None:
+        _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
+    a = N.TailArgs(R, K, counts.data_ptr(), thr.data_ptr(), N.ptr(thr_index), fleet_sums.data_ptr(),
+                   out.tail_ns.data_ptr(), out.total_ns.data_ptr(), out.score.data_ptr(),
+                   N.ptr(calls), N.ptr(out.strag), float(score_thr))
+    N.call("nvrx_histogram_tail_scores", ctypes.byref(a), _stream(stream))
+    return TailScores(out.score, out.tail_ns, out.total_ns, out.strag, calls)
+
+
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,
                scratch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """ref[k] = min_r med[r, k] if every row has k (num > 0), else NaN (reporting.py:255-296)."""

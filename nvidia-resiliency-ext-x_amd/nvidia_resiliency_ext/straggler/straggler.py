@@ -22,7 +22,7 @@ from typing import Any, Deque, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import ops
+from . import dist_utils, histograms, ops
 from .cupti import CuptiManager
 from .interval_tracker import ReportIntervalTracker
 from .reporting import ReportGenerator
@@ -61,6 +61,18 @@ class CustomSection:
     max_elapseds_len: int = 8 * 1024
     cpu_elapsed_times: Deque[float] = dataclasses.field(
         default_factory=lambda: collections.deque(maxlen=CustomSection.max_elapseds_len))
+
+
+@dataclasses.dataclass
+class TailScore:
+    """What ``Detector.kernel_tail_score`` returns for this rank."""
+
+    score: float          # about 1 healthy, lower = more time in the fleet's tail; NaN: no samples
+    tail_ns: int          # weighted counts above the fleet's threshold buckets (ns, a lower bound)
+    total_ns: int         # all weighted counts
+    fleet_share: float    # fleet_tail / fleet_total: the tail's share of the fleet's time
+    is_straggler: bool    # score < threshold (NaN never)
+    top: List[Tuple[str, int]]  # (kernel name, calls above its threshold bucket), most first
 
 
 class Detector:
@@ -180,6 +192,65 @@ class Detector:
             torch.cuda.synchronize()
         names, _, counts = cls.cupti_manager.get_histograms()
         return {n: counts[i].copy() for i, n in enumerate(names)}
+
+    @classmethod
+    def kernel_tail_score(cls, permille: int = 990, threshold: Optional[float] = None,
+                          top: int = 8) -> TailScore:
+        """This rank's tail score over the current report interval: what the median-based scores
+        cannot see, a rank that is slow on every n-th call.  The ranks' kernel histograms
+        (``kernel_histograms``) are summed to the fleet's, T_k is the bucket of the fleet's
+        ``permille`` quantile of kernel k, ``w(b)`` a bucket's lower edge in ns, and
+
+            score = (1 - tail_ns / total_ns) / (1 - fleet_tail / fleet_total)
+
+        with ``tail_ns`` this rank's weighted counts above T_k over its kernels ("ncclDev"
+        kernels are left out, as in the report): about 1 for a healthy rank, lower for one that
+        spends more of its time in the fleet's tail -- the scale of the GPU scores, and
+        ``is_straggler`` is ``score < threshold`` (None: 0.75, ``identify_stragglers``' default).
+        ``top`` is the length of ``TailScore.top``, the (kernel name, calls above T_k) pairs with
+        the most tail calls.  Exact integer sums on the device (include/nvrx_straggler.h).  A
+        slowdown below one bucket (12.5 %) may not cross T_k, and ``permille`` must leave more
+        room than the slow rank's own share of the fleet's samples (8 ranks, every 10th call
+        slow: use 950, not 990).
+
+        A COLLECTIVE, unlike the other ``kernel_*`` calls: it adds one ``all_gather_object`` (the
+        kernel names) and one ``all_reduce`` (SUM of an int64 [kernels, 240] tensor) on the
+        reporter's group, so EVERY rank must call it, at the same point.  Call it BEFORE
+        ``generate_report``, which resets the interval; the report is unchanged by it.  With a
+        world of one, or without a process group, the fleet is the rank itself.  Beyond the
+        reference."""
+        assert cls.initialized
+        pm = ops.tail_permille(permille)
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        group = cls.reporter.group
+        names, _, counts = cls.cupti_manager.get_histograms()  # name-sorted, int64 [n, 240] (host)
+        union = sorted(set().union(*dist_utils.all_gather_object(list(names), group)))
+        col = {n: i for i, n in enumerate(union)}
+        index = np.fromiter((col[n] for n in names), dtype=np.int32, count=len(names))
+        fleet_h = np.zeros((len(union), histograms.BINS), np.int64)
+        fleet_h[index] = counts
+        fleet = torch.from_numpy(fleet_h).to(dist_utils.get_device_for_backend(group))
+        dist_utils.all_reduce(fleet, op=torch.distributed.ReduceOp.SUM, group=group)
+        thr = 0.75 if threshold is None else float(threshold)
+        nan = float("nan")
+        if not names:  # nothing captured on this rank: no score (the collectives above still ran)
+            return TailScore(nan, 0, 0, nan, False, [])
+        dev = cls.reporter._dev()
+        valid = torch.from_numpy(np.fromiter(("ncclDev" not in n for n in union), dtype=np.uint8,
+                                             count=len(union))).to(dev)
+        t_k, sums = ops.histogram_tail_threshold(fleet.to(dev), pm, col_valid=valid)
+        mine = torch.from_numpy(counts.astype(np.uint32).view(np.int32)).to(dev)
+        res = ops.histogram_tail_scores(mine.view(1, len(names), histograms.BINS), t_k, sums,
+                                        score_thr=thr, thr_index=torch.from_numpy(index).to(dev),
+                                        tail_calls=True)
+        ftail, ftotal = (int(v) & (2 ** 64 - 1) for v in sums.tolist())
+        calls = res.tail_calls.view(-1).cpu().numpy().view(np.uint32)
+        order = sorted(range(len(names)), key=lambda k: (-int(calls[k]), names[k]))
+        return TailScore(float(res.score.item()), int(res.tail_ns.item()) & (2 ** 64 - 1),
+                         int(res.total_ns.item()) & (2 ** 64 - 1),
+                         float(ftail) / float(ftotal) if ftotal else nan, bool(res.strag.item()),
+                         [(names[k], int(calls[k])) for k in order[:max(int(top), 0)] if calls[k]])
 
     @classmethod
     def kernel_attribution(cls, top: int = 8, kind: str = "relative"):
