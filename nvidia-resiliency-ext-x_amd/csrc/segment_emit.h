@@ -39,8 +39,8 @@ __device__ __forceinline__ void emit_stats(const nvrx_stats_soa& o, int64_t s, i
     //         in us^2.
     // The quotient is num times the hardware reciprocal refined by Newton steps (~1e-16
     // relative, so at most a rounding-boundary case off the correctly rounded f32) and the root
-    // is the hardware v_sqrt_f32 (~1 ulp): both far inside the FAST bars (2.5e-7 / 1e-6
-    // relative), without the f64 divide and correctly rounded sqrt sequences (~20 of ~400 VALU
+    // is the hardware v_sqrt_f32 (~1 ulp): both inside the FAST bound,
+    // without the f64 divide and correctly rounded sqrt sequences (~20 of ~400 VALU
     // per segment at 1024 samples).
     const double den = 1000.0 * dn;
     const double vq = __builtin_fma(sq, dn, -(se * se));

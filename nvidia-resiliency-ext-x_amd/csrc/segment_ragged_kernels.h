@@ -194,6 +194,7 @@ void seg_stats_list_kernel(RaggedSegs segs, const uint32_t* list, const uint32_t
         unsigned v[PL];
         if (ListPrefetch<PL>::on) {
             issue_loads<PL>(p, n, v);
+            unsigned probes = issue_probes(p, n);
             for (int j = 0; j < m; ++j) {
                 // unconditional prefetch (the last one re-reads the current segment): a load
                 // under a branch would make the waitcnt at the join cover it
@@ -203,9 +204,10 @@ void seg_stats_list_kernel(RaggedSegs segs, const uint32_t* list, const uint32_t
                 desc(j + 1 < m ? j + 1 : j, s2, p2, n2);
                 unsigned w[PL];
                 issue_loads<PL>(p2, n2, w);
+                const unsigned probes2 = issue_probes(p2, n2);
                 int m0;
                 unsigned x0;
-                finish_loads<PL, false>(p, n, v, m0, x0);
+                finish_loads_pivot<PL>(p, n, v, probes, m0, x0);
                 const LeanOut<PL> r = lean_core<PL, false, ListKeepBin<PL>::on>(v, n, m0, x0, hist);
                 if (ListGroup<PL>::on) {
                     res.keep(j, r);
@@ -215,6 +217,7 @@ void seg_stats_list_kernel(RaggedSegs segs, const uint32_t* list, const uint32_t
                 }
 #pragma unroll
                 for (int i = 0; i < PL; ++i) v[i] = w[i];
+                probes = probes2;
                 s = s2;
                 p = p2;
                 n = n2;
@@ -224,7 +227,7 @@ void seg_stats_list_kernel(RaggedSegs segs, const uint32_t* list, const uint32_t
                 if (j) desc(j, s, p, n);
                 int m0;
                 unsigned x0;
-                load_segment<PL, false>(p, n, v, m0, x0);
+                load_segment_pivot<PL>(p, n, v, m0, x0);
                 const LeanOut<PL> r = lean_core<PL, false, ListKeepBin<PL>::on>(v, n, m0, x0, hist);
                 if (ListGroup<PL>::on) {
                     res.keep(j, r);

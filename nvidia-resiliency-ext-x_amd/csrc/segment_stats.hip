@@ -59,7 +59,10 @@ void seg_stats_fast_kernel(Segs segs, int64_t nseg, nvrx_stats_soa out, ColRef c
     unsigned v[PL];
     int m0;
     unsigned x0;
-    load_segment<PL, FULL>(p, n, v, m0, x0);
+    if constexpr (FULL)
+        load_segment<PL, true>(p, n, v, m0, x0);
+    else
+        load_segment_pivot<PL>(p, n, v, m0, x0);
     const LeanOut<PL> r = lean_core<PL, FULL>(v, n, m0, x0, hist);
     emit_stats(out, s, n, r.mn, r.mx, r.d0, r.d1, (double)r.sd, r.sq, r.c, cr);
     // keys of >= 3.76 s take the decoded moments (rare, wave-uniform)

@@ -119,9 +119,18 @@ __device__ __forceinline__ double sd_value(uint64_t b) {
         return __longlong_as_double((long long)b);
 }
 
+// The pivot of the squares is the median of three probes, the samples p[0], p[n / 2] and
+// p[n - 1]: a sample, as the masked bodies' padding has to be, and one that a single outlier
+// cannot be.  The f32 squares round relative to sigma^2 + (pivot - mean)^2, so a pivot far from
+// the bulk costs STD its accuracy; with sample 0 as the pivot a ring whose first call was the
+// slow one did that.
+__device__ __forceinline__ unsigned median3(unsigned a, unsigned b, unsigned c) {
+    return max(min(a, b), min(max(a, b), c));
+}
+
 // !FULL: a segment of n < 64 * PL samples starting m0 slots into its first 16-byte vector
-// (finish_loads set every other slot to x0, sample 0, the pivot: neutral for MIN / MAX, d - c
-// = 0 in the squares).  The pad = 64 * PL - n copies of x0 are taken out again where they
+// (finish_loads_pivot set every other slot to x0, the pivot, a sample: neutral for MIN / MAX,
+// d - c = 0 in the squares).  The pad = 64 * PL - n copies of x0 are taken out again where they
 // count: pad * c from the exact sum; -pad as the initial count of the pivot's bin at every
 // histogram level whose window holds it; and from the candidates of the pivot's bucket (a
 // masked compaction, only when the median's bucket is the pivot's).  The wrapped max / min of
@@ -159,7 +168,15 @@ __device__ __forceinline__ LeanOut<PL> lean_core(unsigned (&v)[PL], int n, int m
     for (int i = 0; i < PL; ++i) v[i] += off;
 
     // ---- exact sum + squares about the pivot c (lane_sums order: pairs, groups of 16) ----
-    const unsigned cp = x0 - mn;  // the padding's d
+    // FULL: x0 is sample 0 and the other two probes of the pivot (slots 32 PL and 64 PL - 1, see
+    // issue_probes) are read here, from registers that already hold d (+ B): taken before MIN is
+    // known they would make the wave wait for its last load ahead of the MIN / MAX pass, which
+    // otherwise runs while the loads land.  !FULL: x0 is the pivot already (and the padding).
+    unsigned cp = x0 - mn;  // the pivot's (and the padding's) d
+    if constexpr (FULL) {
+        constexpr int EM = 32 * PL;  // slot n / 2: register 4 (EM >> 8) of lane (EM & 255) >> 2
+        cp = median3(cp, rl(v[4 * (EM >> 8)], (EM & 255) >> 2) - B, rl(v[PL - 1], 63) - B);
+    }
     unsigned c = cp;
     Sd sd;
     double acc;
@@ -406,21 +423,32 @@ __device__ __forceinline__ void issue_loads(const uint32_t* p, int n, unsigned (
 }
 
 template <int PL, bool FULL>
-__device__ __forceinline__ void finish_loads(const uint32_t* p, int n, unsigned (&v)[PL], int& m0,
+__device__ __forceinline__ void first_sample(const uint32_t* p, const unsigned (&v)[PL], int& m0,
                                              unsigned& x0) {
-    const int lane = lane_id();
     m0 = FULL ? 0 : (int)(((uintptr_t)p & 15) >> 2);
     const unsigned e0 = m0 == 0 ? v[0] : m0 == 1 ? v[1] : m0 == 2 ? v[2] : v[3];
     x0 = __builtin_amdgcn_readlane(e0, 0);
+}
+// the slots outside the segment take x (a sample)
+template <int PL, bool FULL>
+__device__ __forceinline__ void fill_outside(int n, unsigned (&v)[PL], int m0, unsigned x) {
+    const int lane = lane_id();
     // a masked-class segment that happens to fill the wave exactly (configs[3]: every ring at
     // cap = 8192) needs no masking (wave-uniform test)
     if (!FULL && (n != 64 * PL || m0 != 0)) {
 #pragma unroll
         for (int i = 0; i < PL; ++i) {
             const unsigned e = (unsigned)(((i >> 2) * 64 + lane) * 4 + (i & 3) - m0);
-            v[i] = (e < (unsigned)n) ? v[i] : x0;
+            v[i] = (e < (unsigned)n) ? v[i] : x;
         }
     }
+}
+
+template <int PL, bool FULL>
+__device__ __forceinline__ void finish_loads(const uint32_t* p, int n, unsigned (&v)[PL], int& m0,
+                                             unsigned& x0) {
+    first_sample<PL, FULL>(p, v, m0, x0);
+    fill_outside<PL, FULL>(n, v, m0, x0);
 }
 
 template <int PL, bool FULL>
@@ -428,6 +456,29 @@ __device__ __forceinline__ void load_segment(const uint32_t* p, int n, unsigned 
                                              unsigned& x0) {
     issue_loads<PL>(p, n, v);
     finish_loads<PL, FULL>(p, n, v, m0, x0);
+}
+
+// The masked bodies' pivot (lean_core's x0 there: the centre of the f32 squares and the padding
+// value): the median of the three probes p[0], p[n / 2], p[n - 1] (lean_core, above).  Lane 0 /
+// the other lanes load p[n / 2] / p[n - 1] with one more vector load issued behind the segment's
+// own, so it lands with them (n >= 1: both inside the segment); the unmasked bodies find the
+// probes in known registers (lean_core) and load nothing more.
+__device__ __forceinline__ unsigned issue_probes(const uint32_t* p, int n) {
+    return p[lane_id() == 0 ? n >> 1 : n - 1];
+}
+template <int PL>
+__device__ __forceinline__ void finish_loads_pivot(const uint32_t* p, int n, unsigned (&v)[PL],
+                                                   unsigned probes, int& m0, unsigned& x0) {
+    first_sample<PL, false>(p, v, m0, x0);
+    x0 = median3(x0, __builtin_amdgcn_readlane(probes, 0), __builtin_amdgcn_readlane(probes, 1));
+    fill_outside<PL, false>(n, v, m0, x0);
+}
+template <int PL>
+__device__ __forceinline__ void load_segment_pivot(const uint32_t* p, int n, unsigned (&v)[PL],
+                                                   int& m0, unsigned& x0) {
+    issue_loads<PL>(p, n, v);
+    const unsigned probes = issue_probes(p, n);
+    finish_loads_pivot<PL>(p, n, v, probes, m0, x0);
 }
 
 }  // namespace nvrx

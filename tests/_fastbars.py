@@ -23,11 +23,12 @@ STD_RTOL = 1e-6
 LANE_EXACT = 128  # the lane classes (<= 128 records, nvrx_straggler.h) are bit-exact
 
 
-def check_avg_std(g_avg, g_std, ref, xmean, xstd, tag=""):
-    """g_*: GPU float32 arrays; ref: oracle records_stats dict; xmean / xstd: records_moments."""
+def check_avg_std(g_avg, g_std, ref, xmean, xstd, tag="", std_rtol=STD_RTOL):
+    """g_*: GPU float32 arrays; ref: oracle records_stats dict; xmean / xstd: records_moments.
+    std_rtol: the STD bar, one number or one per bucket (tests/_moments_ref.py `std_bound`)."""
     num = ref["num"]
     present = num > 0
-    for f, g, x, tol in (("avg", g_avg, xmean, AVG_RTOL), ("std", g_std, xstd, STD_RTOL)):
+    for f, g, x, tol in (("avg", g_avg, xmean, AVG_RTOL), ("std", g_std, xstd, std_rtol)):
         g = np.asarray(g)
         same = g.view(np.uint32) == ref[f].view(np.uint32)
         short = present & (num <= LANE_EXACT)
@@ -37,4 +38,4 @@ def check_avg_std(g_avg, g_std, ref, xmean, xstd, tag=""):
         ok = same | (err <= tol)
         bad = np.count_nonzero(present & ~ok)
         worst = float(np.max(np.where(present & ~same, err, 0.0))) if present.any() else 0.0
-        assert bad == 0, f"{tag}: {f} outside the FAST bar {tol} in {bad} buckets (worst {worst:.3e})"
+        assert bad == 0, f"{tag}: {f} outside the FAST bar {np.max(tol)} in {bad} buckets (worst {worst:.3e})"

@@ -1,17 +1,20 @@
 """GPU parity: per-kernel statistics (HIP segment_stats) vs the oracle computeStats.
 
 Bar (north_star): NUM / MIN / MAX / MED bit-exact on integer-ns inputs, in both modes;
-EXACT mode also AVG / STD bit-exact; FAST mode AVG / STD are the exact f64 mean /
-population std of the retained samples rounded once to f32, checked (a) against an f64
-numpy reference within 2 f32 ulps and (b) against the oracle's sequential-f32 values
-within rtol 1e-4 (the reference's own accumulation error at n <= 8192).
+EXACT mode also AVG / STD bit-exact; FAST mode AVG / STD are the exact mean / population
+std of the retained samples rounded once to f32, checked against the exact rational moments
+(tests/_moments_ref.py): AVG the correctly rounded f32, STD within the bound of the kernel's
+arithmetic for that segment; AVG also against the oracle's sequential-f32
+value within rtol 1e-4 (the reference's own accumulation error at n <= 8192).  A segment the
+dispatch rule sends to the EXACT kernel (`_moments_cases.sent_to_exact`) carries the oracle's bits.
 """
 import numpy as np
 import pytest
 import torch
 
+import _moments_ref as M
 import oracle as O
-from _fastbars import key_values
+from _moments_cases import edge_segments as _edge_segments, sent_to_exact
 from nvidia_resiliency_ext.straggler import ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -24,14 +27,33 @@ def _oracle_segments(host_ns, nseg, stride, begin, length, cap):
 
 
 def _exact_avg_std(host_ns, nseg, stride, begin, length, cap):
+    """The retained keys of every strided segment, and whether the launch runs the EXACT kernel
+    (the device buffers of these tests start on a 16-byte boundary)."""
     keep = min(length, cap) if cap > 0 else length
-    avg = np.empty(nseg)
-    std = np.empty(nseg)
-    for s in range(nseg):
-        seg = key_values(host_ns[s * stride + begin + length - keep: s * stride + begin + length])
-        avg[s] = seg.mean() / 1000.0
-        std[s] = seg.std() / 1000.0
-    return avg, std
+    aligned = stride % 4 == 0 and (begin + length - keep) % 4 == 0
+    segs = [host_ns[s * stride + begin + length - keep: s * stride + begin + length] for s in range(nseg)]
+    return segs, sent_to_exact(keep, aligned)
+
+
+def _check_moments(g, segs, where=None, tag=""):
+    """FAST AVG / STD of segments `where` (default: all, in order) against the exact moments."""
+    ga, gs = g.avg.numpy(), g.std.numpy()
+    for i, keys in enumerate(segs):
+        s = i if where is None else int(where[i])
+        M.check(ga[s], gs[s], keys, tag=f"{tag} segment {s}")
+
+
+def _check_bulk(g_avg, g_std, x, special, tag=""):
+    """The rows of x vectorised (`_moments_ref.check_batch`); the rows in `special` (edge
+    segments: wide keys, ranges past 2^31) are checked one by one by the caller."""
+    x = x.copy()
+    keep = np.ones(x.shape[0], bool)
+    keep[np.asarray(special)] = False
+    ga, gs = np.asarray(g_avg).copy(), np.asarray(g_std).copy()
+    src = int(np.flatnonzero(keep)[0])
+    x[~keep] = x[src]
+    ga[~keep], gs[~keep] = ga[src], gs[src]
+    M.check_batch(ga, gs, x, tag=tag)
 
 
 def _check(gpu, ref, exact_fields=FIELDS, avg_std=None):
@@ -44,16 +66,16 @@ def _check(gpu, ref, exact_fields=FIELDS, avg_std=None):
         else:
             assert np.array_equal(a, b), (f, a[:8], b[:8])
     if avg_std is not None:
-        # FAST: exact mean/std rounded once to f32.  A segment that does not fit a fast
+        # FAST: exact mean/std rounded once to f32.  A launch whose segments do not fit a fast
         # wave (>8192 slots incl. 16-B misalignment) runs the EXACT kernel instead, whose
-        # AVG/STD are the reference's own (bit-exact with the oracle): accept either.
-        avg, std = avg_std
+        # AVG/STD are the reference's own: demanded bit for bit there, and only there.
+        segs, exact = avg_std
         ga, gs = g.avg.numpy(), g.std.numpy()
-        exact_ref = (ga.view(np.uint32) == ref["avg"].view(np.uint32)) & \
-                    (gs.view(np.uint32) == ref["std"].view(np.uint32))
-        fast_ok = (np.abs(ga - avg) <= 2.5e-7 * np.abs(avg)) & \
-                  (np.abs(gs - std) <= 1e-6 * np.abs(std) + 1e-6)
-        assert np.all(exact_ref | fast_ok), (ga, avg, ref["avg"])
+        if exact:
+            assert np.array_equal(ga.view(np.uint32), ref["avg"].view(np.uint32))
+            assert np.array_equal(gs.view(np.uint32), ref["std"].view(np.uint32))
+        else:
+            _check_moments(g, segs)
         np.testing.assert_allclose(ga, ref["avg"], rtol=1e-4)
 
 
@@ -105,27 +127,6 @@ def test_lengths_and_alignment(mode, length):
             _check(st, ref, avg_std=_exact_avg_std(host, nseg, stride, begin, length, 0))
 
 
-def _edge_segments(n):
-    rng = np.random.default_rng(7)
-    segs = [
-        np.full(n, 12345, np.uint32),                                   # all equal
-        np.where(rng.random(n) < 0.5, 10, 20).astype(np.uint32),       # two values
-        rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32),  # full 32-bit range
-        (2**24 + rng.integers(-3, 4, size=n)).astype(np.uint32),       # u32->f32 rounding edge
-        np.sort(rng.integers(100, 200, size=n).astype(np.uint32)),     # sorted, narrow
-        np.sort(rng.integers(100, 2**31, size=n).astype(np.uint32))[::-1].copy(),  # reverse
-        # one huge bucket: most values clustered, few outliers (forces deeper levels)
-        np.concatenate([np.full(n - min(n, 3), 1_000_000, np.uint32) +
-                        rng.integers(0, 7, size=n - min(n, 3)).astype(np.uint32),
-                        np.array([1, 4_000_000_000, 7][:min(n, 3)], np.uint32)]),
-        (rng.integers(0, 2**20, size=n) * 4096 + 5).astype(np.uint32),  # sparse keys
-        np.zeros(n, np.uint32),                                          # 0-ns durations
-        # tight cluster + one low outlier: variance far below mean^2 (cancellation-prone)
-        np.where(np.arange(n) == n - 1, 10, 100_000 + rng.integers(0, 20, size=n)).astype(np.uint32),
-    ]
-    return segs
-
-
 @pytest.mark.parametrize("mode", [ops.STATS_FAST, ops.STATS_EXACT])
 @pytest.mark.parametrize("n", [1, 2, 5, 64, 100, 1024, 3000, 8192])
 def test_edge_distributions(mode, n):
@@ -138,10 +139,8 @@ def test_edge_distributions(mode, n):
         _check(st, ref, exact_fields=FIELDS + ("avg", "std"))
     else:
         _check(st, ref)
-        avg, std = _exact_avg_std(host, len(segs), n, 0, n, 0)
-        g = st.cpu()
-        np.testing.assert_allclose(g.avg.numpy(), avg, rtol=2.5e-7, atol=1e-30)
-        np.testing.assert_allclose(g.std.numpy(), std, rtol=1e-6, atol=1e-6 * avg.max())
+        assert not sent_to_exact(n, n % 4 == 0)
+        _check_moments(st.cpu(), segs, tag=f"edge n={n}")
 
 
 @pytest.mark.parametrize("mode", [ops.STATS_FAST, ops.STATS_EXACT])
@@ -215,6 +214,7 @@ def test_short_segments_edge_distributions(n):
     ns = torch.from_numpy(host.view(np.int32)).to(DEV)
     st = ops.segment_stats_strided(ns, len(segs), stride, 0, n, cap=0, mode=ops.STATS_FAST)
     _check(st, _oracle_segments(host, len(segs), stride, 0, n, 0))
+    _check_moments(st.cpu(), segs, tag=f"short edge n={n}")
 
 
 def test_config3_shape_with_colref():
@@ -295,9 +295,11 @@ def test_ragged_length_classes(mode, aligned16, cap):
         if mode == ops.STATS_EXACT or keep <= 128:  # lane / workgroup classes: every field
             assert got[3:] == want[3:], (s, keep, got, want)
         else:
-            v = seg[L - keep:].astype(np.float64)
-            assert abs(got[3] - v.mean() / 1000) <= 2.5e-7 * v.mean() / 1000 or got[3] == want[3], s
-            assert abs(got[4] - v.std() / 1000) <= 1e-6 * v.std() / 1000 + 1e-6 or got[4] == want[4], s
+            # the EXACT kernel's values where the dispatch rule sends the segment there, only there
+            if sent_to_exact(keep, aligned16):
+                assert got[3:] == want[3:], (s, keep, got, want)
+            else:
+                M.check(got[3], got[4], seg[L - keep:], tag=f"segment {s} keep {keep}")
     want_ref = O.kernel_ref(num.reshape(rows, ncols), med.reshape(rows, ncols))
     c = col.cpu().numpy()
     missing = c[ncols:] != 0
@@ -337,9 +339,10 @@ def test_ragged_class_boundaries(mode, aligned16):
             assert got[3:] == want[3:], (s, L, got, want)
         else:  # FAST: exact mean / std rounded once, or (a segment too long for a misaligned
             # wave, sent to the workgroup kernel) the reference's own values
-            v = key_values(host[off[s]:off[s + 1]])
-            assert abs(got[3] - v.mean() / 1000) <= 2.5e-7 * v.mean() / 1000 or got[3] == want[3], (s, L)
-            assert abs(got[4] - v.std() / 1000) <= 1e-6 * v.std() / 1000 + 1e-6 or got[4] == want[4], (s, L)
+            if sent_to_exact(int(L), False):  # the call does not promise 16-byte aligned runs
+                assert got[3:] == want[3:], (s, L, got, want)
+            else:
+                M.check(got[3], got[4], host[off[s]:off[s + 1]], tag=f"segment {s} L {L}")
 
 
 @pytest.mark.parametrize("n,mult", [(256, 3601), (512, 3601), (1024, 3550), (256, 7087)])
@@ -364,16 +367,11 @@ def test_grouped_full_segments(n, mult):
     st = ops.segment_stats_strided(ns, nseg, n, 0, n, cap=0, mode=ops.STATS_FAST, col_ref=col, ncols=K)
     ref = _oracle_segments(host, nseg, n, 0, n, 0)
     _check(st, ref)
-    # FAST AVG / STD against the exact moments (vectorised: segments of the random bulk are
-    # below the wide-key threshold; the edge segments take key_values)
+    # FAST AVG / STD against the exact moments: the random bulk vectorised, the edge segments
+    # (wide keys, wide ranges) one by one
     g = st.cpu()
-    x = host.reshape(nseg, n).astype(np.float64)
-    avg, std = x.mean(axis=1) / 1000.0, x.std(axis=1) / 1000.0
-    for w in where:
-        v = key_values(host[w * n:(w + 1) * n])
-        avg[w], std[w] = v.mean() / 1000.0, v.std() / 1000.0
-    np.testing.assert_allclose(g.avg.numpy(), avg, rtol=2.5e-7, atol=1e-30)
-    np.testing.assert_allclose(g.std.numpy(), std, rtol=1e-6, atol=1e-6 * avg.max())
+    _check_bulk(g.avg.numpy(), g.std.numpy(), host.reshape(nseg, n), where, tag=f"group n={n}")
+    _check_moments(g, edges, where, tag=f"group n={n} edge")
     want = O.kernel_ref(ref["num"].reshape(-1, K), ref["med"].reshape(-1, K))
     got = col.cpu().numpy()
     assert np.array_equal(got[:K].view(np.float32), want) and not got[K:].any()
@@ -404,13 +402,8 @@ def test_list_chunk_epilogue(L, W):
     ref = _oracle_segments(host, cnt, L, 0, L, 0)
     _check(st, ref)
     g = st.cpu()
-    x = host.reshape(cnt, L).astype(np.float64)
-    avg, std = x.mean(axis=1) / 1000.0, x.std(axis=1) / 1000.0
-    for w in where:
-        v = key_values(host[w * L:(w + 1) * L])
-        avg[w], std[w] = v.mean() / 1000.0, v.std() / 1000.0
-    np.testing.assert_allclose(g.avg.numpy(), avg, rtol=2.5e-7, atol=1e-30)
-    np.testing.assert_allclose(g.std.numpy(), std, rtol=1e-6, atol=1e-6 * avg.max())
+    _check_bulk(g.avg.numpy(), g.std.numpy(), host.reshape(cnt, L), where, tag=f"list L={L}")
+    _check_moments(g, [edges[i % len(edges)] for i in range(len(where))], where, tag=f"list L={L} edge")
 
 
 @pytest.mark.parametrize("keep,nfull", [(1024, 4 * 8300 + 3), (2048, 4 * 40 + 1), (4096, 4 * 25 + 2),
@@ -458,13 +451,8 @@ def test_full_class_segments(keep, nfull):
         a = getattr(g, f).numpy()[full]
         b = ref[f]
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (f, keep)
-    x = host[idx].astype(np.float64)
-    avg, std = x.mean(axis=1) / 1000.0, x.std(axis=1) / 1000.0
-    for a, _ in zip(at, edges):
-        v = key_values(host[idx[a]])
-        avg[a], std[a] = v.mean() / 1000.0, v.std() / 1000.0
-    np.testing.assert_allclose(g.avg.numpy()[full], avg, rtol=2.5e-7, atol=1e-30)
-    np.testing.assert_allclose(g.std.numpy()[full], std, rtol=1e-6, atol=1e-6 * avg.max())
+    _check_bulk(g.avg.numpy()[full], g.std.numpy()[full], host[idx], at, tag=f"FULL keep={keep}")
+    _check_moments(g, edges, full[at], tag=f"FULL keep={keep} edge")
     for s in np.flatnonzero(lens < keep):  # the other classes, against computeStats
         L = int(lens[s])
         r = O.compute_stats(O.key_to_us(host[off[s]:off[s] + L]))
