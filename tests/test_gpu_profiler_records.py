@@ -205,6 +205,55 @@ def test_profiler_compaction_keeps_retention_semantics():
         p.close()
 
 
+def test_profiler_compaction_leaves_the_retained_log():
+    # the compacted log itself (records_bucket with force_stable + records_unbucket): slot-major,
+    # inside a slot exactly the last `cap` pushes in push order -- against the plain reference
+    # retain() (tests/_records_model.py).  Zipf-distributed pushes over 300 kernels: the first
+    # overflow their rings many times over, the last stay below cap.
+    from _records_model import retain
+
+    cap, nslots = 64, 300
+    p = cupti.KernelProfiler(statsMaxLenPerKernel=cap)
+    try:
+        p.initialize()
+        p.start()
+        rng = np.random.default_rng(300)
+        n = (1 << 22) + 4096  # past the compaction threshold
+        z = rng.zipf(2.0, size=n)
+        slots = np.where(z <= nslots, z - 1, 0).astype(np.uint32)
+        ns = np.arange(n, dtype=np.uint32) + 1000  # distinct: a misplaced record shows
+        for s in range(nslots):
+            assert p.register_kernel(f"k{s:03d}") == s
+        p.push_slots(slots, ns)
+        st = p.get_stats_columns()  # flush -> compaction (log >> retained records)
+
+        def slot_major(all_slots, all_ns):
+            r = retain(np.stack([all_slots, all_ns], 1), np.array([0, all_slots.size]), nslots, cap)
+            lens = np.array([k.size for k in r.kept])
+            return r, np.repeat(np.arange(nslots, dtype=np.uint32), lens), np.concatenate(r.kept)
+
+        r, want_slots, want_ns = slot_major(slots, ns)
+        assert (r.counts > 100 * cap).any() and ((r.counts > 0) & (r.counts < cap)).any()
+        got_slots, got_ns = p.get_records()
+        assert np.array_equal(got_slots, want_slots) and np.array_equal(got_ns, want_ns)
+        assert st.names == [f"k{s:03d}" for s in range(nslots)]
+        assert np.array_equal(st.num, np.minimum(r.counts, cap))
+        # more pushes land behind the compacted log in push order; retention over it keeps what
+        # retention over the whole history keeps
+        more = rng.integers(0, nslots, size=5000).astype(np.uint32)
+        more_ns = np.arange(more.size, dtype=np.uint32) + 1000 + n
+        p.push_slots(more, more_ns)
+        st = p.get_stats_columns()
+        got_slots, got_ns = p.get_records()
+        assert np.array_equal(got_slots, np.concatenate([want_slots, more]))
+        assert np.array_equal(got_ns, np.concatenate([want_ns, more_ns]))
+        r2, _, want2 = slot_major(np.concatenate([slots, more]), np.concatenate([ns, more_ns]))
+        assert np.array_equal(slot_major(got_slots, got_ns)[2], want2)
+        assert np.array_equal(st.num, np.minimum(r2.counts, cap))
+    finally:
+        p.close()
+
+
 def test_cupti_manager_refcount():
     # test_cupti_manager.py:23-87
     m = cupti.CuptiManager(statsMaxLenPerKernel=64)
