@@ -30,7 +30,7 @@
  *   nvrx_records_*         CuptiProfiler::bufferCompleted record loop + CircularBuffer     cupti_src/CuptiProfiler.cpp:168-203, CircularBuffer.h:53-69
  * Beyond the reference (no counterpart there): nvrx_segment_quantiles_*, nvrx_score_attribution,
  * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms,
- * nvrx_histogram_sum / _tail_threshold / _tail_scores.
+ * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -287,6 +287,77 @@ int nvrx_histogram_tail_threshold(const uint64_t* fleet, int64_t K, int32_t perm
                                   const uint8_t* col_valid, int32_t* thr, uint64_t* fleet_sums,
                                   void* stream);
 int nvrx_histogram_tail_scores(const nvrx_tail_args* args, void* stream);
+
+/* Individual tail scores: a row (rank) against its own histogram history -- the individual leg of
+ * the tail scores above, as hist of nvrx_score_args is the individual leg of the median-based
+ * scores.  It sees what the relative tail score cannot: a world of one, a degradation that hits
+ * every rank together, a large share of the ranks slow on every n-th call.  No reference
+ * counterpart.  One fused, stream-ordered pass finds a threshold bucket per (row, kernel) in the
+ * history, scores the current counts against it and folds them into the history.  The definition
+ * is part of the ABI; every sum is an exact integer, so the result is the same on every run.
+ * Inputs: counts C[r][k][b], u32, R rows x K kernels x NVRX_HIST_BINS buckets (what
+ *   nvrx_segment_histogram_* writes; 16-byte aligned, rows contiguous);
+ *   hist, u32, the same buckets, changed in place: the history of row r, slot s, is the 240 counts
+ *   at hist + (r * hist_stride + s) * 240 (16-byte aligned); hist_stride is counted in histograms,
+ *   0 means K;  hist_index[K] (i32) or NULL (identity): s = hist_index[k], a negative entry means
+ *   column k has no history slot; every other entry must be below the stride (not checked);
+ *   col_valid[K] (u8) or NULL (all valid);  permille pm, an integer in [0, 1000];
+ *   skip_rows[R] (u8) or NULL;  mode, a bit set of NVRX_HTAIL_SCORE and NVRX_HTAIL_UPDATE, at least
+ *   one of them;  score_thr.
+ * Terms: w(b) = nvrx_histogram_edge(min(b, 238)) as for the tail scores above;  s = the slot of k;
+ *   H = hist as it stands BEFORE this call;  N = sum_b H[r][s][b] (u64);  n = sum_b C[r][k][b].
+ * SCORE
+ *   eligible     (r, k) iff col_valid[k] != 0, s >= 0, N > 0 and n > 0.
+ *   threshold    T[r][k] = the bucket that holds the history's sample of 0-based rank
+ *                (pm * (N - 1)) / 1000 (64-bit integer division, the product taken exactly): the
+ *                smallest b with sum_{b' <= b} H[r][s][b'] > rank, the rule of step 2 above.
+ *   per row      u64 sums mod 2^64 over the eligible k:
+ *                    total_ns[r]      = sum_k sum_b           C[r][k][b] * w(b)
+ *                    tail_ns[r]       = sum_k sum_{b > T}     C[r][k][b] * w(b)
+ *                    base_total_ns[r] = sum_k sum_b           H[r][s][b] * w(b)
+ *                    base_tail_ns[r]  = sum_k sum_{b > T}     H[r][s][b] * w(b)
+ *                tail_calls[r][k] = sum_{b > T} C[r][k][b] (u32; 0 where not eligible).
+ *   score        in f64, each operation rounded separately, each u64 converted to f64 first:
+ *                    score[r] = (1.0 - tail_ns[r] / total_ns[r]) /
+ *                               (1.0 - base_tail_ns[r] / base_total_ns[r])
+ *                NaN when total_ns[r] == 0, base_total_ns[r] == 0 or the denominator is 0.0;
+ *                strag[r] = score[r] < score_thr (strict; NaN never).  A first interval has no
+ *                history and gives NaN, which is never flagged.
+ * UPDATE
+ *   for every (r, k) with col_valid[k] != 0, s >= 0, and skip_rows NULL or skip_rows[r] == 0:
+ *                    H[r][s][b] = min(H[r][s][b] + C[r][k][b], 2^32 - 1)
+ *   (the sum is formed in 64 bits and saturates: a long run never wraps).  With both bits set the
+ *   score uses the history from before the update.  A flagged interval can be kept out of the
+ *   history without a host round trip: a SCORE call, then an UPDATE call with skip_rows = strag.
+ * Two columns of one row must not map to the same slot, and counts and hist must not overlap;
+ * neither is checked.  Outputs: tail_ns, total_ns, base_tail_ns, base_total_ns [R] u64 (8-byte
+ * aligned), score [R] f64, strag [R] u8 or NULL, tail_calls [R][K] u32 or NULL (ignored without
+ * SCORE).  Without SCORE no score output is touched or needed.  K * 240 and R * K must be below
+ * 2^31.  R == 0 or K == 0 launches nothing.  Stream-ordered: kernels on `stream` only, no
+ * allocation, no synchronisation, no host read-back; capturable as a linear chain.  The four u64
+ * outputs are the accumulators of the pass (cleared on the stream first): they must not alias. */
+#define NVRX_HTAIL_SCORE 1
+#define NVRX_HTAIL_UPDATE 2
+typedef struct nvrx_histtail_args {
+    int64_t R, K;
+    const uint32_t* counts;     /* [R][K][NVRX_HIST_BINS] */
+    uint32_t* hist;             /* [R][hist_stride][NVRX_HIST_BINS], in place */
+    int64_t hist_stride;        /* in histograms; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* [K] or NULL */
+    const uint8_t* skip_rows;   /* [R] or NULL */
+    int32_t permille;
+    int32_t mode;               /* NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE */
+    double score_thr;
+    uint64_t* tail_ns;          /* [R] */
+    uint64_t* total_ns;         /* [R] */
+    uint64_t* base_tail_ns;     /* [R] */
+    uint64_t* base_total_ns;    /* [R] */
+    double* score;              /* [R] */
+    uint8_t* strag;             /* [R] or NULL */
+    uint32_t* tail_calls;       /* [R][K] or NULL */
+} nvrx_histtail_args;
+int nvrx_histogram_history_scores(const nvrx_histtail_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

@@ -5,7 +5,7 @@
 // code + thread-local message.  The profiler handle that replaces the reference's
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
-// histogram_scores.hip and records.hip.
+// histogram_scores.hip, histogram_history.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -295,6 +295,36 @@ int nvrx_histogram_tail_scores(const nvrx_tail_args* a, void* stream) {
     NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0,
                    "nvrx_histogram_tail_scores: counts not 16-byte aligned");
     return hip_status(nvrx::histogram_tail_scores(*a, S(stream)), "nvrx_histogram_tail_scores");
+}
+
+int nvrx_histogram_history_scores(const nvrx_histtail_args* a, void* stream) {
+    const std::string fn("nvrx_histogram_history_scores");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
+                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
+    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                   fn + ": hist_stride below K without hist_index");
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->counts, fn + ": null counts");
+        NVRX_CHECK_ARG(a->hist, fn + ": null hist");
+        if (a->mode & NVRX_HTAIL_SCORE) {
+            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
+            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
+            NVRX_CHECK_ARG(a->score, fn + ": null score");
+        }
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0, fn + ": counts not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
+    if (a->mode & NVRX_HTAIL_SCORE)
+        NVRX_CHECK_ARG((((uintptr_t)a->tail_ns | (uintptr_t)a->total_ns | (uintptr_t)a->base_tail_ns |
+                         (uintptr_t)a->base_total_ns) & 7) == 0,
+                       fn + ": the u64 outputs are not 8-byte aligned");
+    return hip_status(nvrx::histogram_history_scores(*a, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

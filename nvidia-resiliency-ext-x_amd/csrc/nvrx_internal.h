@@ -45,6 +45,8 @@ hipError_t histogram_tail_threshold(const uint64_t* fleet, int64_t K, int permil
                                     const uint8_t* col_valid, int32_t* thr, uint64_t* fleet_sums,
                                     hipStream_t st);
 hipError_t histogram_tail_scores(const nvrx_tail_args& a, hipStream_t st);
+// individual tail scores against the rows' own history (histogram_history.hip)
+hipError_t histogram_history_scores(const nvrx_histtail_args& a, hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

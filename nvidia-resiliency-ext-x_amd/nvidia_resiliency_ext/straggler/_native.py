@@ -76,6 +76,19 @@ class TailArgs(ctypes.Structure):
     ]
 
 
+NVRX_HTAIL_SCORE = 1
+NVRX_HTAIL_UPDATE = 2
+
+
+class HistTailArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("counts", P), ("hist", P), ("hist_stride", i64),
+        ("hist_index", P), ("col_valid", P), ("skip_rows", P), ("permille", i32), ("mode", i32),
+        ("score_thr", f64), ("tail_ns", P), ("total_ns", P), ("base_tail_ns", P),
+        ("base_total_ns", P), ("score", P), ("strag", P), ("tail_calls", P),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -120,6 +133,7 @@ SIGNATURES = {
     "nvrx_histogram_sum": (ctypes.c_int, [P, i64, i64, i32, P, P]),
     "nvrx_histogram_tail_threshold": (ctypes.c_int, [P, i64, i32, P, P, P, P]),
     "nvrx_histogram_tail_scores": (ctypes.c_int, [ctypes.POINTER(TailArgs), P]),
+    "nvrx_histogram_history_scores": (ctypes.c_int, [ctypes.POINTER(HistTailArgs), P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

@@ -79,6 +79,23 @@ class BatchTailScores:
     tail_calls: Optional[torch.Tensor] = None  # [R, K] int32 on the device, on request
 
 
+@dataclass
+class BatchIndividualTailScores:
+    """MatrixReporter.individual_tail_scores: per rank a score from the tail of its histograms
+    against its own history."""
+    score: np.ndarray             # [R] f64, about 1 healthy, lower = more time in its own tail; NaN: no history
+    tail_ns: np.ndarray           # [R] u64 weighted counts above the history's threshold buckets
+    total_ns: np.ndarray          # [R] u64 weighted counts of the kernels scored
+    history_share: np.ndarray     # [R] f64 base_tail / base_total: the tail's share of the history's time
+    stragglers: np.ndarray        # [R] bool, score < threshold (NaN never)
+    base_tail_ns: np.ndarray      # [R] u64
+    base_total_ns: np.ndarray     # [R] u64
+    tail_calls: Optional[torch.Tensor] = None  # [R, K] int32 on the device, on request
+
+
+ABSORB_MODES = ("healthy", "always", "never")
+
+
 @dataclass(eq=False)
 class _ReportBuffers:
     """The device buffers of one report: segment statistics, the per-kernel reference the
@@ -185,6 +202,7 @@ class MatrixReporter:
         self._attr_ref = None  # attribute(): its own column reference and packed outputs per top
         self._attr_out = {}
         self._tail = None  # tail_scores(): fleet histogram and packed outputs, allocated at first use
+        self._htail = None  # individual_tail_scores(): [R][K][240] history and packed outputs, likewise
 
     @property
     def stats(self) -> ops.SegmentStats:
@@ -409,6 +427,75 @@ class MatrixReporter:
                                host[8 * (3 * R + 2) + 4 * kp:].astype(bool),
                                host[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(np.int32)[:K].copy(),
                                res.tail_calls)
+
+    def individual_tail_scores(self, counts: torch.Tensor, permille: int = 990,
+                               threshold: Optional[float] = None, absorb: str = "healthy",
+                               tail_calls: bool = False) -> BatchIndividualTailScores:
+        """A tail score per rank against the rank's OWN history, from the histograms
+        ``histograms()`` returned for this interval (int32 device tensor [R, K, 240]): the
+        individual leg of ``tail_scores``.  It sees what a comparison with the fleet cannot -- a
+        world of one, a degradation that hits every rank together, a large share of the ranks slow
+        on every n-th call.  Per (rank, kernel) T is the bucket of the ``permille`` quantile of the
+        history (kernels filtered by ``col_valid``, without history or without samples in this
+        interval are skipped), ``w(b)`` a bucket's lower edge in ns, and
+
+            score[r] = (1 - tail_ns[r] / total_ns[r]) / (1 - base_tail[r] / base_total[r])
+
+        with ``tail_ns`` / ``base_tail`` the interval's / the history's weighted counts above T:
+        about 1 for a rank that behaves as it did, lower for one that spends more of its time above
+        its own past's quantile.  ``stragglers`` is ``score < threshold`` (None: the reporter's
+        individual threshold).  The first interval has no history: NaN, never flagged.  ``absorb``
+        says which intervals join the history (saturating u32 counts): ``"always"`` -- one fused
+        score-and-update launch; ``"never"`` -- score only; ``"healthy"`` (default) -- a score
+        launch, then an update launch that skips the flagged ranks on the device (no host round
+        trip), so a flagged interval does not teach the history that slow is normal.  Exact integer
+        sums on the device (include/nvrx_straggler.h).  The reporter owns the history, R * K * 960
+        bytes of device memory allocated at first use (``reset_tail_history`` clears it), and the
+        packed outputs; the results come in one device-to-host copy, and the call queues behind
+        reports in flight and changes none of the report's buffers.  ``tail_calls=True`` also
+        returns, on the device, the int32 [R, K] calls above T.  Beyond the reference."""
+        pm = ops.tail_permille(permille)
+        if absorb not in ABSORB_MODES:
+            raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.individual_tail_scores: tail scores across "
+                                      "kernel shards (exchange=True) are not supported")
+        R, K, d = self.R, self.K, self.device
+        if tuple(counts.shape) != (R, K, histograms.BINS):
+            raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
+        self._order_after_inflight()
+        if self._htail is None:
+            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns i64 R][strag u8 R]
+            self._htail = dict(buf=torch.zeros(41 * R, dtype=torch.uint8, device=d),
+                               hist=torch.zeros((R, K, histograms.BINS), dtype=torch.int32, device=d),
+                               calls=None)
+        t = self._htail
+        buf = t["buf"]
+        i64 = buf[:40 * R].view(torch.int64)
+        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
+                                    i64[3 * R:4 * R], i64[4 * R:], buf[40 * R:])
+        if tail_calls and t["calls"] is None:
+            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
+        res = ops.histogram_history_scores(
+            counts, t["hist"], permille=pm, update=absorb == "always", col_valid=self.col_valid,
+            score_thr=self.thr_ind if threshold is None else threshold,
+            tail_calls=t["calls"] if tail_calls else False, out=out)
+        if absorb == "healthy":
+            ops.histogram_history_scores(counts, t["hist"], permille=pm, score=False,
+                                         col_valid=self.col_valid, skip_rows=out.strag)
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        h64 = host[:40 * R].view(np.uint64).reshape(5, R).copy()
+        btail, btotal = h64[3], h64[4]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
+        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
+                                         host[40 * R:].astype(bool), btail, btotal, res.tail_calls)
+
+    def reset_tail_history(self) -> None:
+        """Forget the history of ``individual_tail_scores``: the next interval scores NaN."""
+        if self._htail is not None:
+            self._order_after_inflight()
+            self._htail["hist"].zero_()
 
     def attribute(self, top: int = 8, kind: str = "relative") -> BatchAttribution:
         """Which kernels made each rank's score what it is: per rank the `top` (1..16) kernels

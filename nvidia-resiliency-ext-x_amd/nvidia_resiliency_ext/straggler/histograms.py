@@ -18,6 +18,9 @@ whole run's, and ``quantile_bounds`` brackets any quantile of the merged samples
 tail scores (``ops.histogram_sum`` / ``histogram_tail_threshold`` / ``histogram_tail_scores``,
 ``MatrixReporter.tail_scores``, ``Detector.kernel_tail_score``): a per-rank score from the fleet's
 summed histograms that sees a rank slow on every n-th call, which its median hides.
+``history_scores`` is the host twin of the individual leg (``ops.histogram_history_scores``,
+``MatrixReporter.individual_tail_scores``, ``Detector.kernel_individual_tail_score``): a rank's
+interval against its own summed history, and the history with the interval folded in.
 """
 from __future__ import annotations
 
@@ -174,6 +177,101 @@ def tail_scores(counts, permille: int, col_valid=None) -> TailScores:
     return TailScores(np.asarray(score, np.float64).reshape(R), np.asarray(tail, np.uint64).reshape(R),
                       np.asarray(total, np.uint64).reshape(R), fs, T.astype(np.int64), calls,
                       ftail, ftotal)
+
+
+@dataclass
+class HistoryScores:
+    """``history_scores``: per row the individual tail score, what it was made from, and the
+    history after the call.  With ``score=False`` only ``hist`` is set."""
+    hist: np.ndarray                      # [R, S, 240] u32, the history after the call
+    score: np.ndarray = None              # [R] f64, NaN without eligible weighted samples
+    tail_ns: np.ndarray = None            # [R] u64, current time above the history's thresholds
+    total_ns: np.ndarray = None           # [R] u64
+    base_tail_ns: np.ndarray = None       # [R] u64, the history's time above its thresholds
+    base_total_ns: np.ndarray = None      # [R] u64
+    history_share: np.ndarray = None      # [R] f64 base_tail_ns / base_total_ns (NaN: no history)
+    stragglers: np.ndarray = None         # [R] bool, score < score_thr (NaN never)
+    threshold_bucket: np.ndarray = None   # [R, K] i64, -1: (row, kernel) not eligible
+    tail_calls: np.ndarray = None         # [R, K] i64 calls above the threshold bucket
+
+
+def history_scores(counts, hist, permille: int, *, score: bool = True, update: bool = True,
+                   hist_index=None, col_valid=None, skip_rows=None,
+                   score_thr: float = 0.75) -> HistoryScores:
+    """Individual tail score per row of ``counts`` ([R, K, 240]) against the row's own history
+    ``hist`` ([R, S, 240], left unchanged; int32 arrays are read as u32), the host twin of
+    ``ops.histogram_history_scores`` with the same definition (include/nvrx_straggler.h).  Column
+    k uses slot ``hist_index[k]`` (identity without; negative: none).  A (row, kernel) is scored
+    when it has a slot, ``col_valid``, history (N > 0) and current samples; T is the bucket of the
+    history's sample of rank ``(permille * (N - 1)) // 1000``, and
+
+        score[r] = (1 - tail_ns[r] / total_ns[r]) / (1 - base_tail_ns[r] / base_total_ns[r])
+
+    in Python integers (wrapped to 64 bits like the device's) and three f64 operations.
+    ``update`` returns ``min(H + C, 2**32 - 1)`` as the new history for every column with a slot
+    and ``col_valid`` in the rows ``skip_rows`` does not mark; the score always uses the history
+    as given.  Emulate ``absorb="healthy"`` with a ``score`` call followed by an ``update`` call
+    with ``skip_rows=stragglers``."""
+    pm = _check_permille(permille)
+    if not (score or update):
+        raise ValueError("history_scores: at least one of score and update")
+    c, H = merge(counts), merge(hist)
+    if c.ndim != 3 or c.shape[2] != BINS:
+        raise ValueError(f"counts must have shape [R, K, {BINS}]")
+    R, K, _ = c.shape
+    if H.ndim != 3 or H.shape[0] != R or H.shape[2] != BINS:
+        raise ValueError(f"hist must have shape [R, S, {BINS}]")
+    S = H.shape[1]
+    index = list(range(K)) if hist_index is None else [int(s) for s in np.asarray(hist_index)]
+    if len(index) != K or any(s >= S for s in index):
+        raise ValueError("hist_index must hold K slots below hist.shape[1]")
+    valid = [True] * K if col_valid is None else [bool(v) for v in np.asarray(col_valid)]
+    skip = [False] * R if skip_rows is None else [bool(v) for v in np.asarray(skip_rows)]
+    cols = [(k, s) for k, s in enumerate(index) if s >= 0 and valid[k]]
+    res = HistoryScores(H.astype(np.uint32))
+    if score:
+        w, M, nan = weights(), (1 << 64) - 1, float("nan")
+        sums = np.zeros((4, R), np.uint64)
+        T = np.full((R, K), -1, np.int64)
+        calls = np.zeros((R, K), np.int64)
+        sc, share = [nan] * R, [nan] * R
+        for r in range(R):
+            tl = tt = bl = bt = 0
+            for k, s in cols:
+                h, cur = H[r, s].tolist(), c[r, k].tolist()
+                n = sum(h)
+                if n == 0 or not any(cur):
+                    continue
+                rank, acc = (pm * (n - 1)) // 1000, 0
+                for t, v in enumerate(h):
+                    acc += v
+                    if acc > rank:
+                        break
+                T[r, k] = t
+                tt += sum(v * w[b] for b, v in enumerate(cur) if v)
+                bt += sum(v * w[b] for b, v in enumerate(h) if v)
+                tl += sum(cur[b] * w[b] for b in range(t + 1, BINS) if cur[b])
+                bl += sum(h[b] * w[b] for b in range(t + 1, BINS) if h[b])
+                calls[r, k] = sum(cur[t + 1:]) & 0xFFFFFFFF
+            tl, tt, bl, bt = tl & M, tt & M, bl & M, bt & M
+            sums[:, r] = (tl, tt, bl, bt)
+            if bt:
+                share[r] = float(bl) / float(bt)
+                den = 1.0 - share[r]
+                if tt and den != 0.0:
+                    sc[r] = (1.0 - float(tl) / float(tt)) / den
+        res.score = np.asarray(sc, np.float64).reshape(R)
+        res.tail_ns, res.total_ns, res.base_tail_ns, res.base_total_ns = sums
+        res.history_share = np.asarray(share, np.float64).reshape(R)
+        res.stragglers = res.score < score_thr
+        res.threshold_bucket, res.tail_calls = T, calls
+    if update:
+        new = H.copy()
+        for k, s in cols:
+            new[:, s] = np.minimum(H[:, s] + c[:, k], 0xFFFFFFFF)
+        new[np.asarray(skip, bool)] = H[np.asarray(skip, bool)]
+        res.hist = new.astype(np.uint32)
+    return res
 
 
 def quantile_bounds(counts, permille: int):

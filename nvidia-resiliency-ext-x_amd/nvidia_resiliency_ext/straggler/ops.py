@@ -373,6 +373,104 @@ def histogram_tail_scores(counts: torch.Tensor, thr: torch.Tensor, fleet_sums: t
     return TailScores(out.score, out.tail_ns, out.total_ns, out.strag, calls)
 
 
+@dataclass
+class HistoryTailScores:
+    """Per row of ``histogram_history_scores`` (device tensors): score [R] float64, tail_ns /
+    total_ns / base_tail_ns / base_total_ns [R] int64 (u64 on the device), strag [R] uint8
+    (score < score_thr), tail_calls [R, K] int32 (u32; None when not requested).  Every field is
+    None after an update-only call without ``out``."""
+
+    score: Optional[torch.Tensor] = None
+    tail_ns: Optional[torch.Tensor] = None
+    total_ns: Optional[torch.Tensor] = None
+    base_tail_ns: Optional[torch.Tensor] = None
+    base_total_ns: Optional[torch.Tensor] = None
+    strag: Optional[torch.Tensor] = None
+    tail_calls: Optional[torch.Tensor] = None
+
+    @classmethod
+    def empty(cls, R: int, device) -> "HistoryTailScores":
+        i = lambda: torch.empty(R, dtype=torch.int64, device=device)  # noqa: E731
+        return cls(torch.empty(R, dtype=torch.float64, device=device), i(), i(), i(), i(),
+                   torch.empty(R, dtype=torch.uint8, device=device))
+
+
+def _u8_vector(t, name, n):
+    if t is not None:
+        _tail_tensor(t, name, t.dtype, (n,))
+        if t.element_size() != 1:
+            raise ValueError(f"{name} must be a uint8 / bool tensor of shape [{n}]")
+    return t
+
+
+def histogram_history_scores(counts: torch.Tensor, hist: torch.Tensor, *, permille: int,
+                             score: bool = True, update: bool = True,
+                             hist_index: Optional[torch.Tensor] = None, hist_stride: int = 0,
+                             col_valid: Optional[torch.Tensor] = None,
+                             skip_rows: Optional[torch.Tensor] = None, score_thr: float = 0.75,
+                             tail_calls=False, out: Optional[HistoryTailScores] = None,
+                             stream=None) -> HistoryTailScores:
+    """Individual tail score per row of ``counts`` ([R, K, 240]) against the row's own history
+    ``hist`` (int32 [R, hist_stride or K, 240] holding u32 counts, changed in place), in one fused
+    pass: per (row, kernel) the threshold bucket T is the bucket of the history's sample of rank
+    ``(permille * (N - 1)) // 1000``, and
+
+        score = (1 - tail_ns / total_ns) / (1 - base_tail_ns / base_total_ns)
+
+    with ``tail_ns`` / ``base_tail_ns`` the current / historic weighted counts above T, over the
+    kernels with a history slot, ``col_valid``, history and current samples (NaN without any: a
+    first interval is never flagged).  ``update`` then folds the counts into the history,
+    ``min(H + C, 2**32 - 1)``, except in the rows ``skip_rows`` (uint8 [R]) marks; with both, the
+    score is taken against the history from before the update.  Column k uses slot
+    ``hist_index[k]`` (int32 [K]; negative: no slot, the kernel is left out).  Two columns must not
+    share a slot and ``counts`` must not overlap ``hist`` (neither is checked).
+    ``tail_calls=True`` (or an int32 [R, K] tensor) also counts the calls above T per row and
+    kernel.  ``score=False`` touches no score output.  ``out``: preallocated outputs."""
+    pm = tail_permille(permille)
+    if not (score or update):
+        raise ValueError("histogram_history_scores: at least one of score and update")
+    R, K = _tail_counts(counts)
+    d = counts.device
+    stride = int(hist_stride)
+    if stride < 0 or (stride and hist_index is None and stride < K):
+        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
+    N.require_device(hist, "hist")
+    if hist.dtype not in (torch.int32, torch.uint32) or hist.data_ptr() % 16:
+        raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
+    _tail_tensor(hist, "hist", hist.dtype, (R, stride or K, N.HIST_BINS))
+    if hist_index is not None:
+        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
+    _u8_vector(col_valid, "col_valid", K)
+    _u8_vector(skip_rows, "skip_rows", R)
+    calls = None
+    if score:
+        if out is None:
+            out = HistoryTailScores.empty(R, d)
+        _tail_tensor(out.score, "out.score", torch.float64, (R,))
+        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
+            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
+        if out.strag is not None:
+            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
+        if tail_calls is True:
+            calls = out.tail_calls
+            if calls is None:
+                calls = torch.empty((R, K), dtype=torch.int32, device=d)
+        elif tail_calls is not False and tail_calls is not None:
+            calls = tail_calls
+        if calls is not None:
+            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
+    elif out is None:
+        out = HistoryTailScores()
+    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    a = N.HistTailArgs(R, K, counts.data_ptr(), hist.data_ptr(), stride, N.ptr(hist_index),
+                       N.ptr(col_valid), N.ptr(skip_rows), pm, mode, float(score_thr),
+                       N.ptr(out.tail_ns), N.ptr(out.total_ns), N.ptr(out.base_tail_ns),
+                       N.ptr(out.base_total_ns), N.ptr(out.score), N.ptr(out.strag), N.ptr(calls))
+    N.call("nvrx_histogram_history_scores", ctypes.byref(a), _stream(stream))
+    return HistoryTailScores(out.score, out.tail_ns, out.total_ns, out.base_tail_ns,
+                             out.base_total_ns, out.strag, calls)
+
+
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,
                scratch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """ref[k] = min_r med[r, k] if every row has k (num > 0), else NaN (reporting.py:255-296)."""

@@ -75,6 +75,42 @@ class TailScore:
     top: List[Tuple[str, int]]  # (kernel name, calls above its threshold bucket), most first
 
 
+@dataclasses.dataclass
+class IndividualTailScore:
+    """What ``Detector.kernel_individual_tail_score`` returns for this rank."""
+
+    score: float          # about 1 = as its own past, lower = more time in its own tail; NaN: no history
+    tail_ns: int          # weighted counts above the history's threshold buckets (ns, a lower bound)
+    total_ns: int         # all weighted counts of the kernels scored
+    history_share: float  # base_tail / base_total: the tail's share of the history's time
+    is_straggler: bool    # score < threshold (NaN never)
+    top: List[Tuple[str, int]]  # (kernel name, calls above its threshold bucket), most first
+    intervals: int        # intervals the history has absorbed, this one included if it was
+
+
+class _TailHistory:
+    """The Detector's own histogram history: kernel name -> slot of an int32 [1, capacity, 240]
+    device tensor that grows by doubling."""
+
+    def __init__(self):
+        self.slots: Dict[str, int] = {}
+        self.hist: Optional[torch.Tensor] = None
+        self.intervals = 0
+
+    def index(self, names: Sequence[str], dev) -> np.ndarray:
+        """The slots of the interval's kernels (new names get new slots), the tensor grown to hold them."""
+        for n in names:
+            self.slots.setdefault(n, len(self.slots))
+        cap = 0 if self.hist is None else self.hist.shape[1]
+        if len(self.slots) > cap:
+            grown = torch.zeros((1, max(2 * cap, len(self.slots), 64), histograms.BINS),
+                                dtype=torch.int32, device=dev)
+            if cap:
+                grown[:, :cap] = self.hist
+            self.hist = grown
+        return np.fromiter((self.slots[n] for n in names), dtype=np.int32, count=len(names))
+
+
 class Detector:
     """Straggler detection entry point; class methods only (not instantiable)."""
 
@@ -88,6 +124,7 @@ class Detector:
     reporter: ReportGenerator
     report_interval_tracker: ReportIntervalTracker
     original_callables: Optional[Dict[CallableId, Any]]
+    _tail_history: _TailHistory
 
     def __new__(cls):
         raise RuntimeError(f"class {cls.__name__} should not be instantiated")
@@ -111,9 +148,11 @@ class Detector:
                                                             profiling_interval=profiling_interval)
         cls.initialized = True
         cls.original_callables = {}
+        cls._tail_history = _TailHistory()
 
     @classmethod
     def shutdown(cls):
+        cls._tail_history = _TailHistory()
         cls.cupti_manager.shutdown()
         cls.restore_original_callables()
         cls.cupti_manager = None
@@ -251,6 +290,73 @@ class Detector:
                          int(res.total_ns.item()) & (2 ** 64 - 1),
                          float(ftail) / float(ftotal) if ftotal else nan, bool(res.strag.item()),
                          [(names[k], int(calls[k])) for k in order[:max(int(top), 0)] if calls[k]])
+
+    @classmethod
+    def kernel_individual_tail_score(cls, permille: int = 990, threshold: Optional[float] = None,
+                                     top: int = 8, absorb: str = "healthy") -> IndividualTailScore:
+        """This rank's tail score over the current report interval against its OWN history: the
+        individual leg of ``kernel_tail_score``, as the individual GPU score is of the relative
+        one.  It sees what a comparison with the fleet cannot: a world of one, a degradation that
+        hits every rank together, a large share of the ranks slow on every n-th call.  The
+        Detector keeps, on the device, the summed histograms of the intervals absorbed so far per
+        kernel name; T_k is the bucket of the ``permille`` quantile of kernel k's history, and
+
+            score = (1 - tail_ns / total_ns) / (1 - base_tail / base_total)
+
+        with ``tail_ns`` / ``base_tail`` this interval's / the history's weighted counts above T_k
+        over the kernels that have history and ran in this interval ("ncclDev" kernels are left
+        out, as in the report; a kernel name seen for the first time gets a history slot and is
+        scored from the next interval on).  About 1 for a rank that behaves as it did, lower for
+        one that spends more time above its own past's quantile; ``is_straggler`` is ``score <
+        threshold`` (None: 0.75).  The first interval has no history: NaN, never flagged.
+        ``absorb``: which intervals join the history -- ``"healthy"`` (default) all but flagged
+        ones, so a slow interval does not teach the history that slow is normal, ``"always"``,
+        or ``"never"``.  ``top`` is the length of ``IndividualTailScore.top``.  Exact integer
+        sums on the device (include/nvrx_straggler.h); a slowdown below one bucket (12.5 %) may not
+        cross T_k.  The history costs 960 bytes of device memory per kernel name and is cleared by
+        ``initialize`` / ``shutdown`` and ``reset_tail_history``.
+
+        NOT a collective: local to the rank.  Call it BEFORE ``generate_report``, which resets the
+        interval; it changes neither the report nor any collective.  Beyond the reference."""
+        assert cls.initialized
+        pm = ops.tail_permille(permille)
+        if absorb not in ("healthy", "always", "never"):
+            raise ValueError(f"absorb must be 'healthy', 'always' or 'never', got {absorb!r}")
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        names, _, counts = cls.cupti_manager.get_histograms()  # name-sorted, int64 [n, 240] (host)
+        th = cls._tail_history
+        nan = float("nan")
+        if not names:  # nothing captured: no score, nothing to absorb
+            return IndividualTailScore(nan, 0, 0, nan, False, [], th.intervals)
+        dev = cls.reporter._dev()
+        index = torch.from_numpy(th.index(names, dev)).to(dev)
+        valid = torch.from_numpy(np.fromiter(("ncclDev" not in n for n in names), dtype=np.uint8,
+                                             count=len(names))).to(dev)
+        mine = torch.from_numpy(counts.astype(np.uint32).view(np.int32)).to(dev)
+        mine = mine.view(1, len(names), histograms.BINS)
+        args = dict(permille=pm, hist_index=index, hist_stride=th.hist.shape[1], col_valid=valid)
+        res = ops.histogram_history_scores(mine, th.hist, update=absorb == "always", tail_calls=True,
+                                           score_thr=0.75 if threshold is None else float(threshold),
+                                           **args)
+        if absorb == "healthy":
+            ops.histogram_history_scores(mine, th.hist, score=False, skip_rows=res.strag, **args)
+        M = 2 ** 64 - 1
+        flagged = bool(res.strag.item())
+        if absorb == "always" or (absorb == "healthy" and not flagged):
+            th.intervals += 1
+        btail, btotal = int(res.base_tail_ns.item()) & M, int(res.base_total_ns.item()) & M
+        calls = res.tail_calls.view(-1).cpu().numpy().view(np.uint32)
+        order = sorted(range(len(names)), key=lambda k: (-int(calls[k]), names[k]))
+        return IndividualTailScore(
+            float(res.score.item()), int(res.tail_ns.item()) & M, int(res.total_ns.item()) & M,
+            float(btail) / float(btotal) if btotal else nan, flagged,
+            [(names[k], int(calls[k])) for k in order[:max(int(top), 0)] if calls[k]], th.intervals)
+
+    @classmethod
+    def reset_tail_history(cls) -> None:
+        """Forget the history of ``kernel_individual_tail_score``: the next interval scores NaN."""
+        cls._tail_history = _TailHistory()
 
     @classmethod
     def kernel_attribution(cls, top: int = 8, kind: str = "relative"):
