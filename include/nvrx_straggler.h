@@ -30,7 +30,8 @@
  *   nvrx_records_*         CuptiProfiler::bufferCompleted record loop + CircularBuffer     cupti_src/CuptiProfiler.cpp:168-203, CircularBuffer.h:53-69
  * Beyond the reference (no counterpart there): nvrx_segment_quantiles_*, nvrx_score_attribution,
  * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms,
- * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores.
+ * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores,
+ * nvrx_histogram_tail_base / _tail_attribution.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -358,6 +359,72 @@ typedef struct nvrx_histtail_args {
     uint32_t* tail_calls;       /* [R][K] or NULL */
 } nvrx_histtail_args;
 int nvrx_histogram_history_scores(const nvrx_histtail_args* args, void* stream);
+
+/* Tail score attribution: the kernels behind a rank's tail score.  No reference counterpart.  The
+ * tail scores above flag a row that is slow on every n-th call; this names the kernels, per row
+ * the `top` with the largest excess tail time.  tail_calls counts calls, and a count is not a
+ * cost: a cheap kernel called thousands of times has dozens of calls above its 95 % bucket on a
+ * healthy rank.  The definition is part of the ABI; terms (w(b), T, eligibility) as in the two
+ * sections above.  For a taken element (r, k), as u64 sums mod 2^64:
+ *     tail[r][k]  = sum_{b > T} C[r][k][b] * w(b)        total[r][k] = sum_b C[r][k][b] * w(b)
+ *     calls[r][k] = sum_{b > T} C[r][k][b]  (u32)        btail, btotal: the base's over the same T
+ * The base and T depend on `kind`:
+ *   NVRX_ATTR_RELATIVE    base = the fleet row F[u], u = thr_index ? thr_index[k] : k, given as
+ *                         base[u] = {btail, btotal} from nvrx_histogram_tail_base;  T = thr[u];
+ *                         taken iff u >= 0, thr[u] >= 0 and sum_b C[r][k][b] > 0.
+ *   NVRX_ATTR_INDIVIDUAL  base = H[r][s] as it stands when the call runs (READ ONLY here);  T from H
+ *                         by the rank rule of nvrx_histogram_history_scores;  taken iff eligible
+ *                         there: col_valid[k] != 0, s >= 0, N > 0 and n > 0.
+ * Then in f64, each u64 converted first (round to nearest even), every operation rounded separately:
+ *     share = btail / btotal
+ *     loss  = tail - total * share      (ns; negative when the row's tail is lighter than the base's)
+ * An element whose loss is NaN (btotal == 0: every sample of the base in bucket 0, whose weight is
+ * 0) is left out, like an absent kernel.  Per row, sum_k tail[r][k] over the taken elements is the
+ * score call's tail_ns[r] when that call takes the same elements; loss is the part of that tail
+ * beyond what the base's tail share predicts.
+ * Outputs, row-major, j < top (1 <= top <= NVRX_MAX_ATTRIBUTION):
+ *     idx[r][j]         column of the j-th largest loss (ties: the lower column first;
+ *                       -0.0 == +0.0), -1 beyond the elements taken
+ *     loss[r][j]        f64, NaN where idx = -1
+ *     tail_ns[r][j], total_ns[r][j]   u64, 0 where idx = -1
+ *     tail_calls[r][j]  u32, 0 where idx = -1
+ *     thr_bucket[r][j]  i32 T, -1 where idx = -1
+ *     base_share[r][j]  f64 share, NaN where idx = -1
+ *     loss_all[r][k]    f64, dense [R][K], NaN where not taken: workspace and output
+ * nvrx_histogram_tail_base: base[K][2] (u64, 16-byte aligned) = {btail, btotal} per kernel of
+ *   fleet[K][240] (u64, 16-byte aligned) over b > thr[k], {0, 0} where thr[k] < 0: the per-kernel
+ *   sums nvrx_histogram_tail_threshold adds up, computed once and not per row.
+ * nvrx_histogram_tail_attribution: two kernels on `stream` (every (r, k) has one owner: no atomics,
+ *   no scratch).  counts and hist 16-byte aligned, tail_ns / total_ns / loss / base_share /
+ *   loss_all / base 8-byte aligned.  hist_stride, hist_index, col_valid, permille: as
+ *   nvrx_histogram_history_scores (individual only); thr, thr_index, base: relative only.
+ * K * 240 and R * K must be below 2^31; top outside 1..16 or an unknown kind is an error.  R == 0 or
+ * K == 0 launches nothing.  Stream-ordered: no allocation, no synchronisation, no host read-back;
+ * capturable as a linear chain. */
+typedef struct nvrx_tailattr_args {
+    int64_t R, K;
+    const uint32_t* counts;     /* [R][K][NVRX_HIST_BINS] */
+    int32_t kind, top;          /* NVRX_ATTR_RELATIVE / NVRX_ATTR_INDIVIDUAL; 1..NVRX_MAX_ATTRIBUTION */
+    const int32_t* thr;         /* relative: threshold buckets of the fleet */
+    const int32_t* thr_index;   /* relative: [K] or NULL */
+    const uint64_t* base;       /* relative: [.][2] {btail, btotal}, from nvrx_histogram_tail_base */
+    const uint32_t* hist;       /* individual: [R][hist_stride][NVRX_HIST_BINS], read only */
+    int64_t hist_stride;        /* in histograms; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* individual: [K] or NULL */
+    int32_t permille;           /* individual */
+    int32_t* idx;               /* [R][top] */
+    double* loss;               /* [R][top] */
+    uint64_t* tail_ns;          /* [R][top] */
+    uint64_t* total_ns;         /* [R][top] */
+    uint32_t* tail_calls;       /* [R][top] */
+    int32_t* thr_bucket;        /* [R][top] */
+    double* base_share;         /* [R][top] */
+    double* loss_all;           /* [R][K] */
+} nvrx_tailattr_args;
+int nvrx_histogram_tail_base(const uint64_t* fleet, int64_t K, const int32_t* thr, uint64_t* base,
+                             void* stream);
+int nvrx_histogram_tail_attribution(const nvrx_tailattr_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

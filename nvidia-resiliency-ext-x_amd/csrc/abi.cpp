@@ -5,7 +5,7 @@
 // code + thread-local message.  The profiler handle that replaces the reference's
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
-// histogram_scores.hip, histogram_history.hip and records.hip.
+// histogram_scores.hip, histogram_history.hip, histogram_attribution.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -325,6 +325,58 @@ int nvrx_histogram_history_scores(const nvrx_histtail_args* a, void* stream) {
                          (uintptr_t)a->base_total_ns) & 7) == 0,
                        fn + ": the u64 outputs are not 8-byte aligned");
     return hip_status(nvrx::histogram_history_scores(*a, S(stream)), fn.c_str());
+}
+
+int nvrx_histogram_tail_base(const uint64_t* fleet, int64_t K, const int32_t* thr, uint64_t* base,
+                             void* stream) {
+    if (int rc = check_tail_shape("nvrx_histogram_tail_base", 0, K)) return rc;
+    if (K > 0) {
+        NVRX_CHECK_ARG(fleet, "nvrx_histogram_tail_base: null fleet");
+        NVRX_CHECK_ARG(thr, "nvrx_histogram_tail_base: null thr");
+        NVRX_CHECK_ARG(base, "nvrx_histogram_tail_base: null base");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)fleet & 15) == 0, "nvrx_histogram_tail_base: fleet not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)base & 15) == 0, "nvrx_histogram_tail_base: base not 16-byte aligned");
+    return hip_status(nvrx::histogram_tail_base(fleet, K, thr, base, S(stream)),
+                      "nvrx_histogram_tail_base");
+}
+
+int nvrx_histogram_tail_attribution(const nvrx_tailattr_args* a, void* stream) {
+    const std::string fn("nvrx_histogram_tail_attribution");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
+                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    NVRX_CHECK_ARG(a->kind == NVRX_ATTR_RELATIVE || a->kind == NVRX_ATTR_INDIVIDUAL,
+                   fn + ": unknown kind (NVRX_ATTR_RELATIVE or NVRX_ATTR_INDIVIDUAL)");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    const bool ind = a->kind == NVRX_ATTR_INDIVIDUAL;
+    if (ind) {
+        NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+        NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+        NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                       fn + ": hist_stride below K without hist_index");
+    }
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->counts, fn + ": null counts");
+        NVRX_CHECK_ARG(ind || a->thr, fn + ": the relative kind needs thr");
+        NVRX_CHECK_ARG(ind || a->base, fn + ": the relative kind needs base");
+        NVRX_CHECK_ARG(!ind || a->hist, fn + ": the individual kind needs hist");
+        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
+        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
+        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
+        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
+        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
+        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0, fn + ": counts not 16-byte aligned");
+    NVRX_CHECK_ARG(!ind || ((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
+    NVRX_CHECK_ARG(ind || ((uintptr_t)a->base & 7) == 0, fn + ": base not 8-byte aligned");
+    NVRX_CHECK_ARG((((uintptr_t)a->loss | (uintptr_t)a->tail_ns | (uintptr_t)a->total_ns |
+                     (uintptr_t)a->base_share | (uintptr_t)a->loss_all) & 7) == 0,
+                   fn + ": the 8-byte outputs are not 8-byte aligned");
+    return hip_status(nvrx::histogram_tail_attribution(*a, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

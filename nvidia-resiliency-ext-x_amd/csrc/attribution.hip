@@ -19,61 +19,11 @@
 
 #include "nvrx_common.h"
 #include "nvrx_internal.h"
+#include "topk_select.h"
 
 namespace nvrx {
 
 namespace {
-
-// Larger loss <=> larger key (unsigned).  NaN losses never get a key, so key 0 (the pattern of a
-// negative NaN with every bit set) is free to mean "no candidate".  -0.0 and +0.0 share +0.0's key:
-// they compare equal, so their order is the column order.
-__device__ __forceinline__ uint64_t loss_key(double loss) {
-    const uint64_t b = loss == 0.0 ? 0ull : (uint64_t)__double_as_longlong(loss);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-constexpr int32_t NO_COL = 0x7FFFFFFF;
-
-// (ka, ca) ranks before (kb, cb): larger key, then lower column
-__device__ __forceinline__ bool before(uint64_t ka, int32_t ca, uint64_t kb, int32_t cb) {
-    return ka > kb || (ka == kb && ca < cb);
-}
-
-template <int CTRL>
-__device__ __forceinline__ void best_step(uint64_t& k, int32_t& c) {
-    const unsigned lo = dpp<CTRL>((unsigned)k), hi = dpp<CTRL>((unsigned)(k >> 32));
-    const uint64_t ok = ((uint64_t)hi << 32) | lo;
-    const int32_t oc = (int32_t)dpp<CTRL>((unsigned)c);
-    const bool take = before(ok, oc, k, c);
-    k = take ? ok : k;
-    c = take ? oc : c;
-}
-
-__device__ __forceinline__ uint64_t rl64(uint64_t x, int l) {
-    const unsigned lo = rl((unsigned)x, l), hi = rl((unsigned)(x >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// The wave's best (key, column): after the four in-row steps every lane holds its row's best; the
-// four rows are combined from lanes 0 / 16 / 32 / 48 (uniform).
-__device__ __forceinline__ void wave_best(uint64_t& k, int32_t& c) {
-    best_step<0xB1>(k, c);
-    best_step<0x4E>(k, c);
-    best_step<0x141>(k, c);
-    best_step<0x140>(k, c);
-    uint64_t bk = rl64(k, 0);
-    int32_t bc = (int32_t)rl((unsigned)c, 0);
-#pragma unroll
-    for (int l = 16; l < 64; l += 16) {
-        const uint64_t ok = rl64(k, l);
-        const int32_t oc = (int32_t)rl((unsigned)c, l);
-        const bool take = before(ok, oc, bk, bc);
-        bk = take ? ok : bk;
-        bc = take ? oc : bc;
-    }
-    k = bk;
-    c = bc;
-}
 
 // One element's terms; false when the element is not taken (absent, filtered, no base, MED == 0,
 // NaN loss).  zero_med reports an eligible element with MED == 0.
@@ -160,18 +110,7 @@ __global__ __launch_bounds__(256) void attribution_kernel(nvrx_attribution_args 
             const int32_t col = (int32_t)(k0 + c * 256);
             const int n = FIRST && c + 1 < TOP ? c + 1 : TOP;  // positions from n on are empty
             if (__builtin_amdgcn_ballot_w64(key > ck[n - 1]) == 0) continue;  // wave-uniform skip
-            bool gt[TOP];
-#pragma unroll
-            for (int i = 0; i < TOP; ++i) gt[i] = key > ck[i];
-#pragma unroll
-            for (int i = TOP - 1; i >= 0; --i) {
-                if (i >= n) continue;
-                const bool shift = i > 0 && gt[i > 0 ? i - 1 : 0];
-                const uint64_t pk = ck[i > 0 ? i - 1 : 0];
-                const int32_t pc = cc[i > 0 ? i - 1 : 0];
-                ck[i] = shift ? pk : (gt[i] ? key : ck[i]);
-                cc[i] = shift ? pc : (gt[i] ? col : cc[i]);
-            }
+            NVRX_TOPK_INSERT(TOP, ck, cc, key, col, n);
         }
     };
     batch(tid, std::true_type{});
@@ -217,13 +156,7 @@ __global__ __launch_bounds__(256) void attribution_kernel(nvrx_attribution_args 
         // three waves without it skip the shift
         const bool pop = wk != 0 && cc[0] == wc;
         if (__builtin_amdgcn_ballot_w64(pop) == 0) continue;
-#pragma unroll
-        for (int i = 0; i < TOP - 1; ++i) {
-            ck[i] = pop ? ck[i + 1] : ck[i];
-            cc[i] = pop ? cc[i + 1] : cc[i];
-        }
-        ck[TOP - 1] = pop ? 0ull : ck[TOP - 1];
-        cc[TOP - 1] = pop ? NO_COL : cc[TOP - 1];
+        NVRX_TOPK_POP(TOP, ck, cc, pop);
     }
 
     if (tid < top) {

@@ -47,6 +47,11 @@ hipError_t histogram_tail_threshold(const uint64_t* fleet, int64_t K, int permil
 hipError_t histogram_tail_scores(const nvrx_tail_args& a, hipStream_t st);
 // individual tail scores against the rows' own history (histogram_history.hip)
 hipError_t histogram_history_scores(const nvrx_histtail_args& a, hipStream_t st);
+// tail score attribution (histogram_attribution.hip): base [K][2] u64 {btail, btotal} per fleet
+// kernel; per row the `top` largest excess tail times of either leg
+hipError_t histogram_tail_base(const uint64_t* fleet, int64_t K, const int32_t* thr, uint64_t* base,
+                               hipStream_t st);
+hipError_t histogram_tail_attribution(const nvrx_tailattr_args& a, hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

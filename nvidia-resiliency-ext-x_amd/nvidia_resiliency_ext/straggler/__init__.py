@@ -9,5 +9,6 @@ returns), ``IndividualTailScore`` (what ``Detector.kernel_individual_tail_score`
 from .reporting import (KernelAttribution, Report, ReportGenerator, StragglerId,  # noqa: F401
                         StragglerReport)
 from .statistics import Statistic  # noqa: F401
-from .straggler import CallableId, Detector, IndividualTailScore, TailScore  # noqa: F401
+from .straggler import (CallableId, Detector, IndividualTailScore,  # noqa: F401
+                        KernelTailAttribution, TailScore)
 from . import histograms, reporting  # noqa: F401

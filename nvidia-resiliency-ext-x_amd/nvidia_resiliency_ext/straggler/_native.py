@@ -89,6 +89,15 @@ class HistTailArgs(ctypes.Structure):
     ]
 
 
+class TailAttrArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("counts", P), ("kind", i32), ("top", i32), ("thr", P),
+        ("thr_index", P), ("base", P), ("hist", P), ("hist_stride", i64), ("hist_index", P),
+        ("col_valid", P), ("permille", i32), ("idx", P), ("loss", P), ("tail_ns", P),
+        ("total_ns", P), ("tail_calls", P), ("thr_bucket", P), ("base_share", P), ("loss_all", P),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -134,6 +143,8 @@ SIGNATURES = {
     "nvrx_histogram_tail_threshold": (ctypes.c_int, [P, i64, i32, P, P, P, P]),
     "nvrx_histogram_tail_scores": (ctypes.c_int, [ctypes.POINTER(TailArgs), P]),
     "nvrx_histogram_history_scores": (ctypes.c_int, [ctypes.POINTER(HistTailArgs), P]),
+    "nvrx_histogram_tail_base": (ctypes.c_int, [P, i64, P, P, P]),
+    "nvrx_histogram_tail_attribution": (ctypes.c_int, [ctypes.POINTER(TailAttrArgs), P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

@@ -68,6 +68,25 @@ class BatchAttribution:
 
 
 @dataclass
+class BatchTailAttribution:
+    """``tail_scores(attribute=top)`` / ``individual_tail_scores(attribute=top)``: per rank the
+    `top` kernels with the largest excess tail time, largest first (ties: the lower column)."""
+    kernel: np.ndarray            # [R, top] i32 kernel column (-1: no further kernel taken)
+    loss_ns: np.ndarray           # [R, top] f64 tail_ns - total_ns * base_share, NaN where kernel is -1
+    tail_ns: np.ndarray           # [R, top] u64 the kernel's weighted counts above its threshold bucket
+    total_ns: np.ndarray          # [R, top] u64 all its weighted counts
+    tail_calls: np.ndarray        # [R, top] u32 its calls above the threshold bucket
+    threshold_bucket: np.ndarray  # [R, top] i32 (-1 where kernel is -1)
+    base_share: np.ndarray        # [R, top] f64 the tail's share of the base's time on that kernel
+    loss_all: Optional[torch.Tensor] = None  # [R, K] f64 on the device: every kernel's loss (NaN: not taken)
+
+    @classmethod
+    def unpack(cls, host: np.ndarray, R: int, top: int, loss_all) -> "BatchTailAttribution":
+        """From the host copy of ``ops.TailAttribution.packed``'s buffer."""
+        return cls(*ops.TailAttribution.unpack(host, R, top), loss_all)
+
+
+@dataclass
 class BatchTailScores:
     """MatrixReporter.tail_scores: per rank a score from the tails of the fleet's histograms."""
     score: np.ndarray             # [R] f64, about 1 healthy, lower = more time in the tail; NaN: no samples
@@ -77,6 +96,7 @@ class BatchTailScores:
     stragglers: np.ndarray        # [R] bool, score < threshold (NaN never)
     threshold_bucket: np.ndarray  # [K] i32 bucket T_k of the fleet's quantile (-1: kernel skipped)
     tail_calls: Optional[torch.Tensor] = None  # [R, K] int32 on the device, on request
+    attribution: Optional[BatchTailAttribution] = None  # with attribute > 0
 
 
 @dataclass
@@ -91,6 +111,7 @@ class BatchIndividualTailScores:
     base_tail_ns: np.ndarray      # [R] u64
     base_total_ns: np.ndarray     # [R] u64
     tail_calls: Optional[torch.Tensor] = None  # [R, K] int32 on the device, on request
+    attribution: Optional[BatchTailAttribution] = None  # with attribute > 0
 
 
 ABSORB_MODES = ("healthy", "always", "never")
@@ -370,8 +391,22 @@ class MatrixReporter:
                                           out=flat, accumulate=accumulate)
         return c.view(R, K, histograms.BINS)
 
+    def _tail_attr_buffers(self, t: dict, base_len: int) -> int:
+        """The packed buffer of a tail-score call with ``attribute > 0``: the call's own packed
+        outputs (``base_len`` bytes) followed by the attribution of up to NVRX_MAX_ATTRIBUTION
+        kernels per rank, and the dense loss workspace; allocated once per reporter.  Returns the
+        attribution's offset."""
+        off = (base_len + 7) // 8 * 8
+        if t.get("abuf") is None:
+            n = self.R * ops.N.NVRX_MAX_ATTRIBUTION
+            t["abuf"] = torch.zeros(off + ops.TailAttribution.PACKED * n, dtype=torch.uint8,
+                                    device=self.device)
+            t["loss_all"] = torch.empty((self.R, self.K), dtype=torch.float64, device=self.device)
+        return off
+
     def tail_scores(self, counts: torch.Tensor, permille: int = 990,
-                    threshold: Optional[float] = None, tail_calls: bool = False) -> BatchTailScores:
+                    threshold: Optional[float] = None, tail_calls: bool = False,
+                    attribute: int = 0) -> BatchTailScores:
         """A tail score per rank from the histograms ``histograms()`` returned (int32 device
         tensor [R, K, 240], possibly accumulated over reports): what the median-based scores
         cannot see, a rank that is slow on every n-th call.  The fleet is the sum over ranks, T_k
@@ -386,11 +421,15 @@ class MatrixReporter:
         integer sums on the device (include/nvrx_straggler.h).  A slowdown below one bucket
         (12.5 %) may not cross T_k, and ``permille`` must leave more room than the slow rank's own
         share of the fleet's samples (8 ranks, every 10th call slow: use 950, not 990).
-        ``tail_calls=True`` also returns, on the device, the int32 [R, K] calls above T_k.  It
+        ``tail_calls=True`` also returns, on the device, the int32 [R, K] calls above T_k.
+        ``attribute=top`` (1..16) adds ``.attribution``: per rank the `top` kernels with the largest
+        excess tail time ``tail - total * fleet_share_k`` in ns (``histograms.tail_attribution``),
+        computed on the device and packed into the same device-to-host copy.  It
         queues behind reports in flight and changes none of the report's buffers; its own buffers
         are allocated once per reporter, and the results come in one device-to-host copy.  Beyond
         the reference."""
         pm = ops.tail_permille(permille)
+        top = ops.attribution_request(attribute, "relative")[0] if attribute else 0
         if self.exchange:
             raise NotImplementedError("MatrixReporter.tail_scores: tail scores across kernel "
                                       "shards (exchange=True) are not supported")
@@ -406,11 +445,17 @@ class MatrixReporter:
                               calls=None, kp=kp)
         t = self._tail
         kp, buf = t["kp"], t["buf"]
+        if top:  # the same layout at the head of a longer buffer
+            aoff = self._tail_attr_buffers(t, buf.numel())
+            if t.get("base") is None:
+                t["base"] = torch.empty((K, 2), dtype=torch.int64, device=d)
+            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
+        base_len = t["buf"].numel()
         i64 = buf[:8 * (3 * R + 2)].view(torch.int64)
         thr = buf[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(torch.int32)[:K]
         sums = i64[3 * R:]
         out = ops.TailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                             buf[8 * (3 * R + 2) + 4 * kp:])
+                             buf[8 * (3 * R + 2) + 4 * kp:base_len])
         if tail_calls and t["calls"] is None:
             t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
         ops.histogram_sum(counts, out=t["fleet"])
@@ -418,19 +463,27 @@ class MatrixReporter:
         res = ops.histogram_tail_scores(counts, thr, sums, out=out,
                                         score_thr=self.thr_rel if threshold is None else threshold,
                                         tail_calls=t["calls"] if tail_calls else False)
+        if top:
+            ops.histogram_tail_base(t["fleet"], thr, out=t["base"])
+            ops.histogram_tail_attribution(
+                counts, top=top, kind="relative", thr=thr, base=t["base"],
+                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
         h64 = host[:8 * (3 * R + 2)].view(np.uint64)
         ftail, ftotal = int(h64[3 * R]), int(h64[3 * R + 1])
         return BatchTailScores(h64[:R].view(np.float64).copy(), h64[R:2 * R].copy(),
                                h64[2 * R:3 * R].copy(),
                                float(ftail) / float(ftotal) if ftotal else float("nan"),
-                               host[8 * (3 * R + 2) + 4 * kp:].astype(bool),
+                               host[8 * (3 * R + 2) + 4 * kp:base_len].astype(bool),
                                host[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(np.int32)[:K].copy(),
-                               res.tail_calls)
+                               res.tail_calls,
+                               BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
+                               if top else None)
 
     def individual_tail_scores(self, counts: torch.Tensor, permille: int = 990,
                                threshold: Optional[float] = None, absorb: str = "healthy",
-                               tail_calls: bool = False) -> BatchIndividualTailScores:
+                               tail_calls: bool = False,
+                               attribute: int = 0) -> BatchIndividualTailScores:
         """A tail score per rank against the rank's OWN history, from the histograms
         ``histograms()`` returned for this interval (int32 device tensor [R, K, 240]): the
         individual leg of ``tail_scores``.  It sees what a comparison with the fleet cannot -- a
@@ -453,8 +506,15 @@ class MatrixReporter:
         bytes of device memory allocated at first use (``reset_tail_history`` clears it), and the
         packed outputs; the results come in one device-to-host copy, and the call queues behind
         reports in flight and changes none of the report's buffers.  ``tail_calls=True`` also
-        returns, on the device, the int32 [R, K] calls above T.  Beyond the reference."""
+        returns, on the device, the int32 [R, K] calls above T.  ``attribute=top`` (1..16) adds
+        ``.attribution``: per rank the `top` kernels with the largest excess tail time ``tail -
+        total * history_share_k`` in ns (``histograms.history_attribution``), packed into the same
+        device-to-host copy.  The order on the device is score, attribution, update, so the
+        attribution sees the history the score saw: ``absorb="always"`` then runs a score-only
+        launch, the attribution and an update-only launch -- by the definition the same bits as the
+        fused launch.  Beyond the reference."""
         pm = ops.tail_permille(permille)
+        top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
             raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
         if self.exchange:
@@ -471,25 +531,38 @@ class MatrixReporter:
                                calls=None)
         t = self._htail
         buf = t["buf"]
+        if top:  # the same layout at the head of a longer buffer
+            aoff = self._tail_attr_buffers(t, 41 * R)
+            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
         i64 = buf[:40 * R].view(torch.int64)
         out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                                    i64[3 * R:4 * R], i64[4 * R:], buf[40 * R:])
+                                    i64[3 * R:4 * R], i64[4 * R:], buf[40 * R:41 * R])
         if tail_calls and t["calls"] is None:
             t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
         res = ops.histogram_history_scores(
-            counts, t["hist"], permille=pm, update=absorb == "always", col_valid=self.col_valid,
+            counts, t["hist"], permille=pm, update=absorb == "always" and not top,
+            col_valid=self.col_valid,
             score_thr=self.thr_ind if threshold is None else threshold,
             tail_calls=t["calls"] if tail_calls else False, out=out)
-        if absorb == "healthy":
+        if top:  # between the score and the update: the history the score saw
+            ops.histogram_tail_attribution(
+                counts, top=top, kind="individual", hist=t["hist"], permille=pm,
+                col_valid=self.col_valid,
+                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
+        if absorb == "healthy" or (absorb == "always" and top):
             ops.histogram_history_scores(counts, t["hist"], permille=pm, score=False,
-                                         col_valid=self.col_valid, skip_rows=out.strag)
+                                         col_valid=self.col_valid,
+                                         skip_rows=out.strag if absorb == "healthy" else None)
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
         h64 = host[:40 * R].view(np.uint64).reshape(5, R).copy()
         btail, btotal = h64[3], h64[4]
         with np.errstate(divide="ignore", invalid="ignore"):
             share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
         return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
-                                         host[40 * R:].astype(bool), btail, btotal, res.tail_calls)
+                                         host[40 * R:41 * R].astype(bool), btail, btotal,
+                                         res.tail_calls,
+                                         BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
+                                         if top else None)
 
     def reset_tail_history(self) -> None:
         """Forget the history of ``individual_tail_scores``: the next interval scores NaN."""

@@ -21,6 +21,10 @@ summed histograms that sees a rank slow on every n-th call, which its median hid
 ``history_scores`` is the host twin of the individual leg (``ops.histogram_history_scores``,
 ``MatrixReporter.individual_tail_scores``, ``Detector.kernel_individual_tail_score``): a rank's
 interval against its own summed history, and the history with the interval folded in.
+``tail_attribution`` / ``history_attribution`` are the host twins of the tail score attribution
+(``ops.histogram_tail_attribution``, ``MatrixReporter.tail_scores(attribute=)``,
+``Detector.kernel_tail_score(attribute=)`` and their individual legs): per rank the kernels with
+the largest excess tail time in ns.
 """
 from __future__ import annotations
 
@@ -272,6 +276,155 @@ def history_scores(counts, hist, permille: int, *, score: bool = True, update: b
         new[np.asarray(skip, bool)] = H[np.asarray(skip, bool)]
         res.hist = new.astype(np.uint32)
     return res
+
+
+@dataclass
+class TailAttribution:
+    """``tail_attribution`` / ``history_attribution``: per row the ``top`` kernels with the largest
+    excess tail time, largest first (ties: the lower column)."""
+    idx: np.ndarray         # [R, top] i32 kernel column, -1 beyond the elements taken
+    loss: np.ndarray        # [R, top] f64 ns, tail - total * base_share; NaN where idx is -1
+    tail_ns: np.ndarray     # [R, top] u64 the kernel's weighted counts above T
+    total_ns: np.ndarray    # [R, top] u64 all its weighted counts
+    tail_calls: np.ndarray  # [R, top] u32 its calls above T
+    thr_bucket: np.ndarray  # [R, top] i32 T, -1 where idx is -1
+    base_share: np.ndarray  # [R, top] f64 btail / btotal of the base; NaN where idx is -1
+    loss_all: np.ndarray    # [R, K] f64 every kernel's loss, NaN where not taken
+
+
+_M64 = (1 << 64) - 1
+
+
+def _wsums(h, t, w):
+    """(weighted sum above bucket t, weighted sum, count above t) of one histogram (a list), as
+    the device's wrapped u64 / u32."""
+    total = sum(v * w[b] for b, v in enumerate(h) if v)
+    tail = sum(h[b] * w[b] for b in range(t + 1, BINS) if h[b])
+    return tail & _M64, total & _M64, sum(h[t + 1:]) & 0xFFFFFFFF
+
+
+def _excess(tail, total, btail, btotal):
+    """(share, loss) in f64, every operation rounded separately, the u64 converted first."""
+    nan = float("nan")
+    if btotal:
+        share = float(btail) / float(btotal)
+    else:
+        share = nan if btail == 0 else float("inf")  # IEEE x / 0
+    return share, float(tail) - float(total) * share
+
+
+def _attribution(R, K, top, element) -> TailAttribution:
+    """Rank what ``element(r, k)`` returns -- None, or (loss, tail, total, calls, T, share) -- per
+    row: a stable sort by descending loss over the columns in order, NaN losses left out."""
+    if isinstance(top, bool) or int(top) != top or not 1 <= top <= 16:
+        raise ValueError(f"top must be an int in [1, 16], got {top!r}")
+    top = int(top)
+    res = TailAttribution(np.full((R, top), -1, np.int32), np.full((R, top), np.nan),
+                          np.zeros((R, top), np.uint64), np.zeros((R, top), np.uint64),
+                          np.zeros((R, top), np.uint32), np.full((R, top), -1, np.int32),
+                          np.full((R, top), np.nan), np.full((R, K), np.nan))
+    for r in range(R):
+        terms = {}
+        for k in range(K):
+            e = element(r, k)
+            if e is not None and e[0] == e[0]:
+                terms[k] = e
+                res.loss_all[r, k] = e[0]
+        ks = np.fromiter(terms, dtype=np.int64, count=len(terms))
+        order = ks[np.argsort(-res.loss_all[r, ks], kind="stable")][:top]
+        for j, k in enumerate(order.tolist()):
+            loss, tail, total, calls, t, share = terms[k]
+            res.idx[r, j], res.loss[r, j], res.thr_bucket[r, j] = k, loss, t
+            res.tail_ns[r, j], res.total_ns[r, j] = tail, total
+            res.tail_calls[r, j], res.base_share[r, j] = calls, share
+    return res
+
+
+def tail_attribution(counts, permille: int, top: int, col_valid=None, *, fleet=None,
+                     thr_index=None) -> TailAttribution:
+    """The kernels behind the tail score of each row of ``counts`` ([R, K, 240]): per row the
+    ``top`` (1..16) kernels with the largest excess tail time
+
+        loss = tail - total * (fleet_tail_k / fleet_total_k)          (ns, f64)
+
+    where ``tail`` / ``total`` are the row's weighted counts of kernel k above its threshold bucket
+    T_k / in all buckets and the fleet's the same sums of the fleet's histogram: the part of the
+    row's tail beyond what the fleet's tail share predicts.  A count of tail calls is not a cost;
+    this is.  The host twin of ``ops.histogram_tail_base`` -> ``histogram_tail_attribution(kind=
+    "relative")`` with the same definition (include/nvrx_straggler.h): Python integers (wrapped to
+    64 bits like the device's), three f64 operations, a stable sort.  The fleet is the sum over
+    rows, or ``fleet`` ([Kf, 240]) with column k using fleet kernel ``thr_index[k]`` (negative:
+    none); ``col_valid`` is over the fleet's kernels.  A kernel without a threshold bucket, without
+    samples in the row, or with a NaN loss (a fleet wholly in bucket 0) is left out."""
+    pm = _check_permille(permille)
+    c = merge(counts)
+    if c.ndim != 3 or c.shape[2] != BINS:
+        raise ValueError(f"counts must have shape [R, K, {BINS}]")
+    R, K, _ = c.shape
+    if fleet is None:
+        F = c.sum(0)
+    else:
+        F = merge(fleet) if np.asarray(fleet).dtype != np.uint64 else np.asarray(fleet)
+    T = tail_threshold(F, pm) if F.shape[0] else np.zeros(0, np.int64)
+    if col_valid is not None:
+        T = np.where(np.asarray(col_valid).astype(bool), T, -1)
+    index = list(range(K)) if thr_index is None else [int(u) for u in np.asarray(thr_index)]
+    if len(index) != K or any(u >= F.shape[0] for u in index):
+        raise ValueError("thr_index must hold K fleet kernels below fleet.shape[0]")
+    w = weights()
+    base = {u: _wsums(F[u].tolist(), int(T[u]), w)[:2] for u in set(index) if u >= 0 and T[u] >= 0}
+    rows = c.tolist()
+
+    def element(r, k):
+        u = index[k]
+        if u not in base or not any(rows[r][k]):
+            return None
+        t = int(T[u])
+        tail, total, calls = _wsums(rows[r][k], t, w)
+        share, loss = _excess(tail, total, *base[u])
+        return loss, tail, total, calls, t, share
+
+    return _attribution(R, K, top, element)
+
+
+def history_attribution(counts, hist, permille: int, top: int, hist_index=None,
+                        col_valid=None) -> TailAttribution:
+    """The kernels behind the individual tail score of each row: as ``tail_attribution`` with the
+    row's own history ``hist`` ([R, S, 240], read only) as the base, T from the history by the rank
+    rule of ``history_scores``, over the (row, kernel) elements eligible there (a slot,
+    ``col_valid``, history and current samples).  The host twin of
+    ``ops.histogram_tail_attribution(kind="individual")``."""
+    pm = _check_permille(permille)
+    c, H = merge(counts), merge(hist)
+    if c.ndim != 3 or c.shape[2] != BINS:
+        raise ValueError(f"counts must have shape [R, K, {BINS}]")
+    R, K, _ = c.shape
+    if H.ndim != 3 or H.shape[0] != R or H.shape[2] != BINS:
+        raise ValueError(f"hist must have shape [R, S, {BINS}]")
+    index = list(range(K)) if hist_index is None else [int(s) for s in np.asarray(hist_index)]
+    if len(index) != K or any(s >= H.shape[1] for s in index):
+        raise ValueError("hist_index must hold K slots below hist.shape[1]")
+    valid = [True] * K if col_valid is None else [bool(v) for v in np.asarray(col_valid)]
+    w = weights()
+
+    def element(r, k):
+        s = index[k]
+        if s < 0 or not valid[k]:
+            return None
+        h, cur = H[r, s].tolist(), c[r, k].tolist()
+        n = sum(h)
+        if n == 0 or not any(cur):
+            return None
+        rank, acc = (pm * (n - 1)) // 1000, 0
+        for t, v in enumerate(h):
+            acc += v
+            if acc > rank:
+                break
+        tail, total, calls = _wsums(cur, t, w)
+        share, loss = _excess(tail, total, *_wsums(h, t, w)[:2])
+        return loss, tail, total, calls, t, share
+
+    return _attribution(R, K, top, element)
 
 
 def quantile_bounds(counts, permille: int):

@@ -11,6 +11,7 @@ import numbers
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -469,6 +470,144 @@ def histogram_history_scores(counts: torch.Tensor, hist: torch.Tensor, *, permil
     N.call("nvrx_histogram_history_scores", ctypes.byref(a), _stream(stream))
     return HistoryTailScores(out.score, out.tail_ns, out.total_ns, out.base_tail_ns,
                              out.base_total_ns, out.strag, calls)
+
+
+def histogram_tail_base(fleet: torch.Tensor, thr: torch.Tensor, out: Optional[torch.Tensor] = None,
+                        stream=None) -> torch.Tensor:
+    """Per kernel of a fleet histogram (int64 [K, 240]) its weighted {tail, total} ns over the
+    threshold bucket ``thr[k]`` (int32 [K], from ``histogram_tail_threshold``) as int64 [K, 2] (u64
+    on the device; {0, 0} where ``thr[k] < 0``): the base of the relative tail attribution, the
+    per-kernel terms ``histogram_tail_threshold`` adds up into ``fleet_sums``."""
+    N.require_device(fleet, "fleet")
+    if fleet.dim() != 2:
+        raise ValueError("fleet must be a contiguous int64 tensor of shape [K, 240]")
+    K = fleet.shape[0]
+    _tail_tensor(fleet, "fleet", torch.int64, (K, N.HIST_BINS))
+    _tail_tensor(thr, "thr", torch.int32, (K,))
+    if out is None:
+        out = torch.empty((K, 2), dtype=torch.int64, device=fleet.device)
+    _tail_tensor(out, "out", torch.int64, (K, 2))
+    if out.data_ptr() % 16:
+        raise ValueError("out must be 16-byte aligned")
+    N.call("nvrx_histogram_tail_base", fleet.data_ptr(), K, thr.data_ptr(), out.data_ptr(),
+           _stream(stream))
+    return out
+
+
+@dataclass
+class TailAttribution:
+    """Per row of ``histogram_tail_attribution`` (device tensors), the ``top`` kernels with the
+    largest excess tail time, largest first: idx [R, top] int32 column (-1: fewer kernels taken),
+    loss [R, top] float64 ns (NaN where idx is -1), tail_ns / total_ns [R, top] int64 (u64 on the
+    device), tail_calls [R, top] int32 (u32), thr_bucket [R, top] int32, base_share [R, top]
+    float64, and the dense loss_all [R, K] float64 (NaN where the kernel is not taken)."""
+
+    idx: torch.Tensor
+    loss: torch.Tensor
+    tail_ns: torch.Tensor
+    total_ns: torch.Tensor
+    tail_calls: torch.Tensor
+    thr_bucket: torch.Tensor
+    base_share: torch.Tensor
+    loss_all: torch.Tensor
+
+    # bytes of one (row, j) slot of the packed form: loss, tail_ns, total_ns, base_share (8 each),
+    # idx, tail_calls, thr_bucket (4 each)
+    PACKED = 44
+
+    @classmethod
+    def empty(cls, R: int, K: int, top: int, device) -> "TailAttribution":
+        return cls.packed(torch.empty(cls.PACKED * R * top, dtype=torch.uint8, device=device), R, top,
+                          torch.empty((R, K), dtype=torch.float64, device=device))
+
+    @classmethod
+    def packed(cls, buf: torch.Tensor, R: int, top: int, loss_all: torch.Tensor) -> "TailAttribution":
+        """Views of the [R, top] outputs in one 8-byte aligned uint8 buffer of PACKED * R * top
+        bytes (8-byte fields first), so that one copy moves them all; ``unpack`` reads it back."""
+        n = R * top
+        q = buf[:32 * n].view(torch.int64).view(4, R, top)
+        d = buf[32 * n:44 * n].view(torch.int32).view(3, R, top)
+        return cls(d[0], q[0].view(torch.float64), q[1], q[2], d[1], d[2], q[3].view(torch.float64),
+                   loss_all)
+
+    @staticmethod
+    def unpack(host: np.ndarray, R: int, top: int):
+        """The host copy of a ``packed`` buffer as numpy arrays [R, top]: (idx i32, loss f64,
+        tail_ns u64, total_ns u64, tail_calls u32, thr_bucket i32, base_share f64)."""
+        n = R * top
+        q = host[:32 * n].view(np.uint64).reshape(4, R, top).copy()
+        d = host[32 * n:44 * n].view(np.int32).reshape(3, R, top).copy()
+        return (d[0], q[0].view(np.float64), q[1], q[2], d[1].view(np.uint32), d[2],
+                q[3].view(np.float64))
+
+
+def histogram_tail_attribution(counts: torch.Tensor, *, top: int, kind: str,
+                               thr: Optional[torch.Tensor] = None,
+                               thr_index: Optional[torch.Tensor] = None,
+                               base: Optional[torch.Tensor] = None,
+                               hist: Optional[torch.Tensor] = None,
+                               hist_index: Optional[torch.Tensor] = None, hist_stride: int = 0,
+                               col_valid: Optional[torch.Tensor] = None,
+                               permille: Optional[int] = None,
+                               out: Optional[TailAttribution] = None,
+                               stream=None) -> TailAttribution:
+    """The kernels behind a tail score: per row of ``counts`` ([R, K, 240]) the ``top`` (1..16)
+    kernels with the largest excess tail time ``loss = tail - total * (btail / btotal)`` in ns,
+    where ``tail`` / ``total`` are the (row, kernel)'s weighted counts above its threshold bucket T
+    / in all buckets and ``btail`` / ``btotal`` the base's (include/nvrx_straggler.h).
+    kind="relative": the base is the fleet -- ``thr`` (int32, ``histogram_tail_threshold``) and
+    ``base`` (int64 [., 2], ``histogram_tail_base``), column k using entry ``thr_index[k]`` (int32
+    [K]; negative: left out).  kind="individual": the base is the row's own history ``hist`` (int32
+    [R, hist_stride or K, 240], read only) with T at ``permille`` of the history, over the elements
+    ``histogram_history_scores`` scores (``hist_index``, ``col_valid``).  Two launches, no scratch;
+    ``out``: preallocated outputs (``out.loss_all`` is also the workspace)."""
+    top, kind_code = attribution_request(top, kind)
+    R, K = _tail_counts(counts)
+    d = counts.device
+    stride, pm = 0, 0
+    if kind_code == N.NVRX_ATTR_RELATIVE:
+        if thr is None or base is None:
+            raise ValueError("kind='relative' needs thr and base")
+        N.require_device(thr, "thr")
+        if thr.dtype != torch.int32 or thr.dim() != 1 or not thr.is_contiguous():
+            raise ValueError("thr must be a contiguous int32 tensor")
+        _tail_tensor(base, "base", torch.int64, (thr.numel(), 2))
+        if thr_index is None:
+            if thr.numel() != K:
+                raise ValueError("thr must hold K entries (or pass thr_index)")
+        else:
+            _tail_tensor(thr_index, "thr_index", torch.int32, (K,))
+        hist = hist_index = col_valid = None
+    else:
+        if hist is None or permille is None:
+            raise ValueError("kind='individual' needs hist and permille")
+        pm = tail_permille(permille)
+        stride = int(hist_stride)
+        if stride < 0 or (stride and hist_index is None and stride < K):
+            raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
+        N.require_device(hist, "hist")
+        if hist.dtype not in (torch.int32, torch.uint32) or hist.data_ptr() % 16:
+            raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
+        _tail_tensor(hist, "hist", hist.dtype, (R, stride or K, N.HIST_BINS))
+        if hist_index is not None:
+            _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
+        _u8_vector(col_valid, "col_valid", K)
+        thr = thr_index = base = None
+    if out is None:
+        out = TailAttribution.empty(R, K, top, d)
+    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
+                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
+                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
+        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
+    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    a = N.TailAttrArgs(R, K, counts.data_ptr(), kind_code, top, N.ptr(thr), N.ptr(thr_index),
+                       N.ptr(base), N.ptr(hist), stride, N.ptr(hist_index), N.ptr(col_valid), pm,
+                       out.idx.data_ptr(), out.loss.data_ptr(), out.tail_ns.data_ptr(),
+                       out.total_ns.data_ptr(), out.tail_calls.data_ptr(),
+                       out.thr_bucket.data_ptr(), out.base_share.data_ptr(),
+                       out.loss_all.data_ptr())
+    N.call("nvrx_histogram_tail_attribution", ctypes.byref(a), _stream(stream))
+    return out
 
 
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,

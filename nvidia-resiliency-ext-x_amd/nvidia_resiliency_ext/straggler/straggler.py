@@ -64,6 +64,19 @@ class CustomSection:
 
 
 @dataclasses.dataclass
+class KernelTailAttribution:
+    """One kernel behind a tail score (``kernel_tail_score(attribute=)`` and its individual leg)."""
+
+    name: str
+    loss_ns: float        # tail_ns - total_ns * base_share: tail time beyond what the base predicts
+    tail_ns: int          # the kernel's weighted counts above its threshold bucket (ns, a lower bound)
+    total_ns: int         # all its weighted counts
+    tail_calls: int       # its calls above the threshold bucket
+    threshold_us: float   # upper edge of the threshold bucket, as ``histograms.edges_us``
+    base_share: float     # the tail's share of the base's (fleet's / history's) time on this kernel
+
+
+@dataclasses.dataclass
 class TailScore:
     """What ``Detector.kernel_tail_score`` returns for this rank."""
 
@@ -73,6 +86,7 @@ class TailScore:
     fleet_share: float    # fleet_tail / fleet_total: the tail's share of the fleet's time
     is_straggler: bool    # score < threshold (NaN never)
     top: List[Tuple[str, int]]  # (kernel name, calls above its threshold bucket), most first
+    attribution: Optional[List[KernelTailAttribution]] = None  # with attribute > 0, largest loss first
 
 
 @dataclasses.dataclass
@@ -86,6 +100,7 @@ class IndividualTailScore:
     is_straggler: bool    # score < threshold (NaN never)
     top: List[Tuple[str, int]]  # (kernel name, calls above its threshold bucket), most first
     intervals: int        # intervals the history has absorbed, this one included if it was
+    attribution: Optional[List[KernelTailAttribution]] = None  # with attribute > 0, largest loss first
 
 
 class _TailHistory:
@@ -200,6 +215,21 @@ class Detector:
         """Per-kernel statistics from the device record log (name-sorted mapping)."""
         return cls.cupti_manager.get_results_columns()
 
+    @staticmethod
+    def _tail_attribution(names, mine, top, kind, **base) -> List[KernelTailAttribution]:
+        """The `top` kernels behind this rank's tail score: two launches and one small
+        device-to-host copy of the packed [1, top] outputs."""
+        buf = torch.empty(ops.TailAttribution.PACKED * top, dtype=torch.uint8, device=mine.device)
+        out = ops.TailAttribution.packed(
+            buf, 1, top, torch.empty((1, len(names)), dtype=torch.float64, device=mine.device))
+        ops.histogram_tail_attribution(mine, top=top, kind=kind, out=out, **base)
+        idx, loss, tail, total, calls, thr, share = (v[0] for v in ops.TailAttribution.unpack(
+            buf.cpu().numpy(), 1, top))
+        edges = histograms.edges_us()
+        return [KernelTailAttribution(names[int(k)], float(loss[j]), int(tail[j]), int(total[j]),
+                                      int(calls[j]), float(edges[int(thr[j]) + 1]), float(share[j]))
+                for j, k in enumerate(idx) if k >= 0]
+
     @classmethod
     def kernel_quantiles(cls, permille: Sequence[int] = (500, 900, 990)) -> Dict[str, Tuple[float, ...]]:
         """Duration quantiles (us) of every kernel captured in the current report interval:
@@ -234,7 +264,7 @@ class Detector:
 
     @classmethod
     def kernel_tail_score(cls, permille: int = 990, threshold: Optional[float] = None,
-                          top: int = 8) -> TailScore:
+                          top: int = 8, attribute: int = 0) -> TailScore:
         """This rank's tail score over the current report interval: what the median-based scores
         cannot see, a rank that is slow on every n-th call.  The ranks' kernel histograms
         (``kernel_histograms``) are summed to the fleet's, T_k is the bucket of the fleet's
@@ -247,7 +277,10 @@ class Detector:
         spends more of its time in the fleet's tail -- the scale of the GPU scores, and
         ``is_straggler`` is ``score < threshold`` (None: 0.75, ``identify_stragglers``' default).
         ``top`` is the length of ``TailScore.top``, the (kernel name, calls above T_k) pairs with
-        the most tail calls.  Exact integer sums on the device (include/nvrx_straggler.h).  A
+        the most tail calls.  A count is not a cost: ``attribute=n`` (1..16) adds
+        ``TailScore.attribution``, the n kernels with the largest excess tail time ``tail_ns -
+        total_ns * fleet_share_k`` in ns as ``KernelTailAttribution``, largest first, computed on
+        the device (no further collective).  Exact integer sums on the device (include/nvrx_straggler.h).  A
         slowdown below one bucket (12.5 %) may not cross T_k, and ``permille`` must leave more
         room than the slow rank's own share of the fleet's samples (8 ranks, every 10th call
         slow: use 950, not 990).
@@ -260,6 +293,7 @@ class Detector:
         reference."""
         assert cls.initialized
         pm = ops.tail_permille(permille)
+        ntop = ops.attribution_request(attribute, "relative")[0] if attribute else 0
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         group = cls.reporter.group
@@ -274,26 +308,35 @@ class Detector:
         thr = 0.75 if threshold is None else float(threshold)
         nan = float("nan")
         if not names:  # nothing captured on this rank: no score (the collectives above still ran)
-            return TailScore(nan, 0, 0, nan, False, [])
+            return TailScore(nan, 0, 0, nan, False, [], [] if ntop else None)
         dev = cls.reporter._dev()
         valid = torch.from_numpy(np.fromiter(("ncclDev" not in n for n in union), dtype=np.uint8,
                                              count=len(union))).to(dev)
-        t_k, sums = ops.histogram_tail_threshold(fleet.to(dev), pm, col_valid=valid)
+        fleet = fleet.to(dev)
+        t_k, sums = ops.histogram_tail_threshold(fleet, pm, col_valid=valid)
         mine = torch.from_numpy(counts.astype(np.uint32).view(np.int32)).to(dev)
-        res = ops.histogram_tail_scores(mine.view(1, len(names), histograms.BINS), t_k, sums,
-                                        score_thr=thr, thr_index=torch.from_numpy(index).to(dev),
+        mine = mine.view(1, len(names), histograms.BINS)
+        index_d = torch.from_numpy(index).to(dev)
+        res = ops.histogram_tail_scores(mine, t_k, sums, score_thr=thr, thr_index=index_d,
                                         tail_calls=True)
+        attribution = None
+        if ntop:
+            attribution = cls._tail_attribution(names, mine, ntop, "relative", thr=t_k,
+                                                thr_index=index_d,
+                                                base=ops.histogram_tail_base(fleet, t_k))
         ftail, ftotal = (int(v) & (2 ** 64 - 1) for v in sums.tolist())
         calls = res.tail_calls.view(-1).cpu().numpy().view(np.uint32)
         order = sorted(range(len(names)), key=lambda k: (-int(calls[k]), names[k]))
         return TailScore(float(res.score.item()), int(res.tail_ns.item()) & (2 ** 64 - 1),
                          int(res.total_ns.item()) & (2 ** 64 - 1),
                          float(ftail) / float(ftotal) if ftotal else nan, bool(res.strag.item()),
-                         [(names[k], int(calls[k])) for k in order[:max(int(top), 0)] if calls[k]])
+                         [(names[k], int(calls[k])) for k in order[:max(int(top), 0)] if calls[k]],
+                         attribution)
 
     @classmethod
     def kernel_individual_tail_score(cls, permille: int = 990, threshold: Optional[float] = None,
-                                     top: int = 8, absorb: str = "healthy") -> IndividualTailScore:
+                                     top: int = 8, absorb: str = "healthy",
+                                     attribute: int = 0) -> IndividualTailScore:
         """This rank's tail score over the current report interval against its OWN history: the
         individual leg of ``kernel_tail_score``, as the individual GPU score is of the relative
         one.  It sees what a comparison with the fleet cannot: a world of one, a degradation that
@@ -311,7 +354,10 @@ class Detector:
         threshold`` (None: 0.75).  The first interval has no history: NaN, never flagged.
         ``absorb``: which intervals join the history -- ``"healthy"`` (default) all but flagged
         ones, so a slow interval does not teach the history that slow is normal, ``"always"``,
-        or ``"never"``.  ``top`` is the length of ``IndividualTailScore.top``.  Exact integer
+        or ``"never"``.  ``top`` is the length of ``IndividualTailScore.top``.  ``attribute=n``
+        (1..16) adds ``IndividualTailScore.attribution``, the n kernels with the largest excess
+        tail time against the history the score saw (``KernelTailAttribution``, largest first).
+        Exact integer
         sums on the device (include/nvrx_straggler.h); a slowdown below one bucket (12.5 %) may not
         cross T_k.  The history costs 960 bytes of device memory per kernel name and is cleared by
         ``initialize`` / ``shutdown`` and ``reset_tail_history``.
@@ -322,13 +368,14 @@ class Detector:
         pm = ops.tail_permille(permille)
         if absorb not in ("healthy", "always", "never"):
             raise ValueError(f"absorb must be 'healthy', 'always' or 'never', got {absorb!r}")
+        ntop = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         names, _, counts = cls.cupti_manager.get_histograms()  # name-sorted, int64 [n, 240] (host)
         th = cls._tail_history
         nan = float("nan")
         if not names:  # nothing captured: no score, nothing to absorb
-            return IndividualTailScore(nan, 0, 0, nan, False, [], th.intervals)
+            return IndividualTailScore(nan, 0, 0, nan, False, [], th.intervals, [] if ntop else None)
         dev = cls.reporter._dev()
         index = torch.from_numpy(th.index(names, dev)).to(dev)
         valid = torch.from_numpy(np.fromiter(("ncclDev" not in n for n in names), dtype=np.uint8,
@@ -336,11 +383,16 @@ class Detector:
         mine = torch.from_numpy(counts.astype(np.uint32).view(np.int32)).to(dev)
         mine = mine.view(1, len(names), histograms.BINS)
         args = dict(permille=pm, hist_index=index, hist_stride=th.hist.shape[1], col_valid=valid)
-        res = ops.histogram_history_scores(mine, th.hist, update=absorb == "always", tail_calls=True,
+        res = ops.histogram_history_scores(mine, th.hist, update=absorb == "always" and not ntop,
+                                           tail_calls=True,
                                            score_thr=0.75 if threshold is None else float(threshold),
                                            **args)
-        if absorb == "healthy":
-            ops.histogram_history_scores(mine, th.hist, score=False, skip_rows=res.strag, **args)
+        attribution = None
+        if ntop:  # between the score and the update: against the history the score saw
+            attribution = cls._tail_attribution(names, mine, ntop, "individual", hist=th.hist, **args)
+        if absorb == "healthy" or (absorb == "always" and ntop):
+            ops.histogram_history_scores(mine, th.hist, score=False,
+                                         skip_rows=res.strag if absorb == "healthy" else None, **args)
         M = 2 ** 64 - 1
         flagged = bool(res.strag.item())
         if absorb == "always" or (absorb == "healthy" and not flagged):
@@ -351,7 +403,8 @@ class Detector:
         return IndividualTailScore(
             float(res.score.item()), int(res.tail_ns.item()) & M, int(res.total_ns.item()) & M,
             float(btail) / float(btotal) if btotal else nan, flagged,
-            [(names[k], int(calls[k])) for k in order[:max(int(top), 0)] if calls[k]], th.intervals)
+            [(names[k], int(calls[k])) for k in order[:max(int(top), 0)] if calls[k]], th.intervals,
+            attribution)
 
     @classmethod
     def reset_tail_history(cls) -> None:
