@@ -31,7 +31,8 @@
  * Beyond the reference (no counterpart there): nvrx_segment_quantiles_*, nvrx_score_attribution,
  * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms,
  * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores,
- * nvrx_histogram_tail_base / _tail_attribution.
+ * nvrx_histogram_tail_base / _tail_attribution, nvrx_segment_fleet_histogram_ragged,
+ * nvrx_segment_tail_scores_ragged.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -288,6 +289,47 @@ int nvrx_histogram_tail_threshold(const uint64_t* fleet, int64_t K, int32_t perm
                                   const uint8_t* col_valid, int32_t* thr, uint64_t* fleet_sums,
                                   void* stream);
 int nvrx_histogram_tail_scores(const nvrx_tail_args* args, void* stream);
+
+/* The same tail scores straight from ragged segments, without the counts matrix (960 B per row and
+ * kernel: more than the samples themselves where most segments hold a few, as the buckets of
+ * record streams do).  No reference counterpart.  Segments as for nvrx_segment_histogram_ragged:
+ * segment r * K + k is row r, kernel k; the last min(len, cap) samples are retained; seg_len[s] <= 0
+ * contributes nothing; seg_len NULL: seg_off holds R * K + 1 offsets.  By definition
+ *   nvrx_segment_fleet_histogram_ragged  writes (accumulate != 0: adds) into fleet[K][240] (u64,
+ *     16-byte aligned) what is equal to nvrx_histogram_sum applied to the counts
+ *     nvrx_segment_histogram_ragged would write into a zeroed matrix;
+ *   nvrx_segment_tail_scores_ragged  writes into tail_ns, total_ns (u64, 8-byte aligned), score,
+ *     strag (or NULL) and tail_calls (or NULL; [R][K], written in full) what is equal to
+ *     nvrx_histogram_tail_scores applied to those counts, thr / thr_index / fleet_sums / score_thr
+ *     as there (steps 4 and 6 of the definition above);
+ * nvrx_histogram_tail_threshold on the fleet goes between the two.  Every sum is an exact integer,
+ * so the results equal the dense chain's bit for bit and are identical from run to run.
+ * K * 240 and R * K must be below 2^31, the retained run at most NVRX_MAX_SEGMENT.  R == 0 or K == 0
+ * launches nothing (outputs untouched).  Stream-ordered: kernels on `stream` only, no allocation,
+ * no synchronisation, no host read-back; the three calls form a linear sequence that can be
+ * captured in a graph. */
+typedef struct nvrx_segtail_args {
+    int64_t R, K;
+    const uint32_t* ns;         /* duration keys */
+    const int64_t* seg_off;     /* [R * K] (+ 1 without seg_len) */
+    const int32_t* seg_len;     /* [R * K] or NULL */
+    int64_t max_len, cap;
+    int32_t aligned16;          /* the caller's word that every retained run starts 16-byte aligned */
+    const int32_t* thr;         /* threshold buckets, from nvrx_histogram_tail_threshold */
+    const int32_t* thr_index;   /* [K] or NULL */
+    const uint64_t* fleet_sums; /* [2] {fleet_tail, fleet_total} */
+    uint64_t* tail_ns;          /* [R] */
+    uint64_t* total_ns;         /* [R] */
+    double* score;              /* [R] */
+    uint32_t* tail_calls;       /* [R][K] or NULL */
+    uint8_t* strag;             /* [R] or NULL */
+    double score_thr;
+} nvrx_segtail_args;
+int nvrx_segment_fleet_histogram_ragged(const uint32_t* ns, const int64_t* seg_off,
+                                        const int32_t* seg_len, int64_t R, int64_t K,
+                                        int64_t max_len, int64_t cap, int32_t aligned16,
+                                        int32_t accumulate, uint64_t* fleet, void* stream);
+int nvrx_segment_tail_scores_ragged(const nvrx_segtail_args* args, void* stream);
 
 /* Individual tail scores: a row (rank) against its own histogram history -- the individual leg of
  * the tail scores above, as hist of nvrx_score_args is the individual leg of the median-based

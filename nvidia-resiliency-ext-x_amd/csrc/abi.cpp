@@ -5,7 +5,7 @@
 // code + thread-local message.  The profiler handle that replaces the reference's
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
-// histogram_scores.hip, histogram_history.hip, histogram_attribution.hip and records.hip.
+// histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -377,6 +377,47 @@ int nvrx_histogram_tail_attribution(const nvrx_tailattr_args* a, void* stream) {
                      (uintptr_t)a->base_share | (uintptr_t)a->loss_all) & 7) == 0,
                    fn + ": the 8-byte outputs are not 8-byte aligned");
     return hip_status(nvrx::histogram_tail_attribution(*a, S(stream)), fn.c_str());
+}
+
+// tail scores straight from ragged segments (segment_tail.hip).  aligned16 is part of the
+// addressing the entries share with nvrx_segment_histogram_ragged; these kernels read by sample
+// and are correct for either value.
+int nvrx_segment_fleet_histogram_ragged(const uint32_t* ns, const int64_t* seg_off,
+                                        const int32_t* seg_len, int64_t R, int64_t K,
+                                        int64_t max_len, int64_t cap, int32_t aligned16,
+                                        int32_t accumulate, uint64_t* fleet, void* stream) {
+    const char* fn = "nvrx_segment_fleet_histogram_ragged";
+    (void)aligned16;
+    if (int rc = check_tail_shape(fn, R, K)) return rc;
+    if (int rc = check_ragged(fn, ns, seg_off, R * K, (int64_t)1 << 31, max_len, cap)) return rc;
+    NVRX_CHECK_ARG(R == 0 || K == 0 || fleet, std::string(fn) + ": null fleet");
+    NVRX_CHECK_ARG(((uintptr_t)seg_off & 7) == 0, std::string(fn) + ": seg_off not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)fleet & 15) == 0, std::string(fn) + ": fleet not 16-byte aligned");
+    return hip_status(nvrx::segment_fleet_histogram_ragged(ns, seg_off, seg_len, R, K, max_len, cap,
+                                                           accumulate != 0, fleet, S(stream)),
+                      fn);
+}
+
+int nvrx_segment_tail_scores_ragged(const nvrx_segtail_args* a, void* stream) {
+    const std::string fn("nvrx_segment_tail_scores_ragged");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
+                              a->max_len, a->cap))
+        return rc;
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->thr, fn + ": null thr");
+        NVRX_CHECK_ARG(a->fleet_sums, fn + ": null fleet_sums");
+        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+        NVRX_CHECK_ARG(a->score, fn + ": null score");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->fleet_sums & 7) == 0, fn + ": fleet_sums not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
+    return hip_status(nvrx::segment_tail_scores_ragged(*a, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

@@ -52,6 +52,12 @@ hipError_t histogram_history_scores(const nvrx_histtail_args& a, hipStream_t st)
 hipError_t histogram_tail_base(const uint64_t* fleet, int64_t K, const int32_t* thr, uint64_t* base,
                                hipStream_t st);
 hipError_t histogram_tail_attribution(const nvrx_tailattr_args& a, hipStream_t st);
+// tail scores straight from ragged segments, no counts matrix (segment_tail.hip): segment
+// r * K + k is row r, column k
+hipError_t segment_fleet_histogram_ragged(const uint32_t* ns, const int64_t* seg_off,
+                                          const int32_t* seg_len, int64_t R, int64_t K, int64_t max_len,
+                                          int64_t cap, int accumulate, uint64_t* fleet, hipStream_t st);
+hipError_t segment_tail_scores_ragged(const nvrx_segtail_args& a, hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

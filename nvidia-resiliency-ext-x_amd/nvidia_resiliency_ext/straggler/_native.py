@@ -76,6 +76,15 @@ class TailArgs(ctypes.Structure):
     ]
 
 
+class SegTailArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("ns", P), ("seg_off", P), ("seg_len", P), ("max_len", i64),
+        ("cap", i64), ("aligned16", i32), ("thr", P), ("thr_index", P), ("fleet_sums", P),
+        ("tail_ns", P), ("total_ns", P), ("score", P), ("tail_calls", P), ("strag", P),
+        ("score_thr", f64),
+    ]
+
+
 NVRX_HTAIL_SCORE = 1
 NVRX_HTAIL_UPDATE = 2
 
@@ -145,6 +154,8 @@ SIGNATURES = {
     "nvrx_histogram_history_scores": (ctypes.c_int, [ctypes.POINTER(HistTailArgs), P]),
     "nvrx_histogram_tail_base": (ctypes.c_int, [P, i64, P, P, P]),
     "nvrx_histogram_tail_attribution": (ctypes.c_int, [ctypes.POINTER(TailAttrArgs), P]),
+    "nvrx_segment_fleet_histogram_ragged": (ctypes.c_int, [P, P, P, i64, i64, i64, i64, i32, i32, P, P]),
+    "nvrx_segment_tail_scores_ragged": (ctypes.c_int, [ctypes.POINTER(SegTailArgs), P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

@@ -224,6 +224,7 @@ class MatrixReporter:
         self._attr_out = {}
         self._tail = None  # tail_scores(): fleet histogram and packed outputs, allocated at first use
         self._htail = None  # individual_tail_scores(): [R][K][240] history and packed outputs, likewise
+        self._rtail = None  # tail_scores_records(): bucketing work tensors, fleet histogram, packed outputs
 
     @property
     def stats(self) -> ops.SegmentStats:
@@ -479,6 +480,74 @@ class MatrixReporter:
                                res.tail_calls,
                                BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
                                if top else None)
+
+    def tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor, permille: int = 990,
+                            threshold: Optional[float] = None,
+                            tail_calls: bool = False) -> BatchTailScores:
+        """The tail scores of ``tail_scores`` for the record streams ``report_records`` takes
+        (recs [n, 2] int32 {slot, ns}, rec_off [R + 1] int64, device), over the windows that
+        report retains (the last ``cap`` records of every rank and kernel) -- without the
+        [R, K, 240] counts, which for record streams would be several times the records
+        themselves.  The streams are bucketed with every bucket written out, then two passes
+        over the buckets (``ops.segment_fleet_histogram_ragged``, ``ops.histogram_tail_threshold``,
+        ``ops.segment_tail_scores_ragged``) give, bit for bit, what ``tail_scores`` gives on the
+        counts of those buckets (``histograms.segment_tail_scores`` on the host).  It queues
+        behind reports in flight and touches none of the report's buffers: the bucketing goes
+        into work tensors of its own, allocated at first use and grown on demand; the results
+        come in one device-to-host copy.  ``.attribution`` stays None.  Beyond the reference."""
+        pm = ops.tail_permille(permille)
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.tail_scores_records: tail scores across "
+                                      "kernel shards (exchange=True) are not supported")
+        R, K, d = self.R, self.K, self.device
+        if rec_off.numel() != R + 1:
+            raise ValueError(f"rec_off must hold {R + 1} offsets")
+        self._order_after_inflight()
+        if self._rtail is None:
+            # packed as tail_scores packs:
+            # [score f64 R][tail_ns i64 R][total_ns i64 R][fleet_sums i64 2][thr i32 K+pad][strag u8 R]
+            kp = (K + 1) // 2 * 2
+            self._rtail = dict(buf=torch.zeros(8 * (3 * R + 2) + 4 * kp + R, dtype=torch.uint8, device=d),
+                               fleet=torch.empty((K, histograms.BINS), dtype=torch.int64, device=d),
+                               calls=None, kp=kp, bucket=None)
+        t = self._rtail
+        kp, buf = t["kp"], t["buf"]
+        n = recs.shape[0]
+        need = ops.records_bucket_capacity(n, R, K)
+        if t["bucket"] is None or t["bucket"][2].numel() < need:
+            t["bucket"] = (torch.empty(R * K, dtype=torch.int64, device=d),
+                           torch.empty(R * K, dtype=torch.int32, device=d),
+                           torch.empty(max(need, 1), dtype=torch.int32, device=d),
+                           torch.empty(R * K, dtype=torch.int32, device=d))
+        base_len = buf.numel()
+        i64 = buf[:8 * (3 * R + 2)].view(torch.int64)
+        thr = buf[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(torch.int32)[:K]
+        sums = i64[3 * R:]
+        out = ops.TailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
+                             buf[8 * (3 * R + 2) + 4 * kp:base_len])
+        if tail_calls and t["calls"] is None:
+            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
+        # records_bucket writes every bucket out (records_stats reduces the tiny ones in LDS and
+        # marks them seg_len < 0); the windows are already trimmed to `cap`, their starts padded
+        # to 16 bytes
+        seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=t["bucket"])
+        max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
+        ops.segment_fleet_histogram_ragged(out_ns, seg_off, seg_len, K, max_len, aligned16=True,
+                                           out=t["fleet"])
+        ops.histogram_tail_threshold(t["fleet"], pm, col_valid=self.col_valid, thr=thr, fleet_sums=sums)
+        res = ops.segment_tail_scores_ragged(
+            out_ns, seg_off, seg_len, K, max_len, thr, sums, aligned16=True, out=out,
+            score_thr=self.thr_rel if threshold is None else threshold,
+            tail_calls=t["calls"] if tail_calls else False)
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        h64 = host[:8 * (3 * R + 2)].view(np.uint64)
+        ftail, ftotal = int(h64[3 * R]), int(h64[3 * R + 1])
+        return BatchTailScores(h64[:R].view(np.float64).copy(), h64[R:2 * R].copy(),
+                               h64[2 * R:3 * R].copy(),
+                               float(ftail) / float(ftotal) if ftotal else float("nan"),
+                               host[8 * (3 * R + 2) + 4 * kp:base_len].astype(bool),
+                               host[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(np.int32)[:K].copy(),
+                               res.tail_calls, None)
 
     def individual_tail_scores(self, counts: torch.Tensor, permille: int = 990,
                                threshold: Optional[float] = None, absorb: str = "healthy",

@@ -25,6 +25,9 @@ interval against its own summed history, and the history with the interval folde
 (``ops.histogram_tail_attribution``, ``MatrixReporter.tail_scores(attribute=)``,
 ``Detector.kernel_tail_score(attribute=)`` and their individual legs): per rank the kernels with
 the largest excess tail time in ns.
+``segment_counts`` / ``segment_tail_scores`` are the host twins of the tail scores taken straight
+from ragged segments, without the counts (``ops.segment_fleet_histogram_ragged``,
+``ops.segment_tail_scores_ragged``, ``MatrixReporter.tail_scores_records``).
 """
 from __future__ import annotations
 
@@ -181,6 +184,39 @@ def tail_scores(counts, permille: int, col_valid=None) -> TailScores:
     return TailScores(np.asarray(score, np.float64).reshape(R), np.asarray(tail, np.uint64).reshape(R),
                       np.asarray(total, np.uint64).reshape(R), fs, T.astype(np.int64), calls,
                       ftail, ftotal)
+
+
+def segment_counts(keys, seg_off, seg_len, K: int, cap: int = 0) -> np.ndarray:
+    """Histograms of ragged segments of duration keys as int64 [R, K, 240]: segment ``r * K + k``
+    is ``keys[seg_off[g] : seg_off[g] + seg_len[g]]`` (``seg_len`` None: ``seg_off`` holds one more
+    offset), of which the last ``cap`` samples are retained (0: all); a length <= 0 counts
+    nothing.  What ``ops.segment_histogram_ragged`` writes into zeroed counts."""
+    keys, off = np.asarray(keys), np.asarray(seg_off, np.int64)
+    if isinstance(K, bool) or int(K) != K or K < 0:
+        raise ValueError(f"K must be a non-negative int, got {K!r}")
+    lens = np.diff(off) if seg_len is None else np.asarray(seg_len, np.int64)
+    nseg = lens.size
+    if (K == 0 and nseg) or (K and nseg % K) or off.size < nseg:
+        raise ValueError("the segments must be R * K, with an offset each")
+    c = np.zeros((nseg, BINS), np.int64)
+    for g in range(nseg):
+        n = int(lens[g])
+        if n <= 0:
+            continue
+        e = int(off[g]) + n
+        keep = cap if 0 < cap < n else n
+        c[g] = np.bincount(bucket_of(keys[e - keep:e]), minlength=BINS)
+    return c.reshape(nseg // K if K else 0, K, BINS)
+
+
+def segment_tail_scores(keys, seg_off, seg_len, K: int, permille: int, cap: int = 0,
+                        col_valid=None) -> TailScores:
+    """Tail score per row straight from ragged segments of duration keys (``segment_counts``'s
+    addressing), the host twin of ``ops.segment_fleet_histogram_ragged`` ->
+    ``histogram_tail_threshold`` -> ``segment_tail_scores_ragged`` and of
+    ``MatrixReporter.tail_scores_records``: ``tail_scores`` (Python-integer sums, three f64
+    operations) over the retained windows' counts."""
+    return tail_scores(segment_counts(keys, seg_off, seg_len, K, cap), permille, col_valid)
 
 
 @dataclass

@@ -374,6 +374,95 @@ def histogram_tail_scores(counts: torch.Tensor, thr: torch.Tensor, fleet_sums: t
     return TailScores(out.score, out.tail_ns, out.total_ns, out.strag, calls)
 
 
+def _segment_rows(ns, seg_off, seg_len, K):
+    """The ragged triple of the segment tail calls, segment r * K + k being row r, column k;
+    returns R."""
+    if isinstance(K, bool) or not isinstance(K, numbers.Integral) or K < 0:
+        raise ValueError(f"K must be a non-negative int, got {K!r}")
+    nseg = _check_ragged(ns, seg_off, seg_len)
+    if not seg_off.is_contiguous() or (seg_len is not None and not seg_len.is_contiguous()):
+        raise ValueError("seg_off and seg_len must be contiguous")
+    if seg_len is not None and seg_len.numel() != nseg:
+        raise ValueError("seg_off and seg_len must hold one entry per segment")
+    if K == 0:
+        if nseg > 0:
+            raise ValueError("K = 0 takes no segments")
+        return 0
+    if nseg < 0 or nseg % K:
+        raise ValueError(f"the segments must be R * K = a multiple of {K}, got {nseg}")
+    return nseg // K
+
+
+def segment_fleet_histogram_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
+                                   seg_len: Optional[torch.Tensor], K: int, max_len: int,
+                                   cap: int = 0, aligned16: bool = False,
+                                   out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                                   stream=None) -> torch.Tensor:
+    """The fleet histogram straight from the ragged segments of ``segment_histogram_ragged``
+    (segment r * K + k: row r, kernel k), without the [R, K, 240] counts: int64 [K, 240] (u64 on
+    the device), equal to ``histogram_sum(segment_histogram_ragged(...))`` into zeroed counts.
+    ``out``: the tensor to write, or with ``accumulate=True`` to add to (then required)."""
+    _histogram_request(out, accumulate)
+    R = _segment_rows(ns, seg_off, seg_len, K)
+    if out is None:
+        out = torch.empty((K, N.HIST_BINS), dtype=torch.int64, device=ns.device)
+    _tail_tensor(out, "out", torch.int64, (K, N.HIST_BINS))
+    if R == 0 and not accumulate:
+        out.zero_()  # the sum of no rows (the C call launches nothing)
+    N.call("nvrx_segment_fleet_histogram_ragged", ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len),
+           R, K, max_len, cap, int(aligned16), int(bool(accumulate)), out.data_ptr(),
+           _stream(stream))
+    return out
+
+
+def segment_tail_scores_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
+                               seg_len: Optional[torch.Tensor], K: int, max_len: int,
+                               thr: torch.Tensor, fleet_sums: torch.Tensor, *, cap: int = 0,
+                               aligned16: bool = False, score_thr: float = 0.75,
+                               thr_index: Optional[torch.Tensor] = None, tail_calls=False,
+                               out: Optional[TailScores] = None, stream=None) -> TailScores:
+    """Tail score per row straight from the ragged segments (segment r * K + k: row r, kernel k),
+    equal to ``histogram_tail_scores`` on the counts ``segment_histogram_ragged`` would write into
+    a zeroed [R, K, 240] tensor; ``thr``, ``fleet_sums``, ``thr_index``, ``score_thr``,
+    ``tail_calls`` and ``out`` as there."""
+    R = _segment_rows(ns, seg_off, seg_len, K)
+    d = ns.device
+    N.require_device(thr, "thr")
+    if thr.dtype != torch.int32 or thr.dim() != 1 or not thr.is_contiguous():
+        raise ValueError("thr must be a contiguous int32 tensor")
+    if thr_index is None:
+        if thr.numel() != K:
+            raise ValueError("thr must hold K entries (or pass thr_index)")
+    else:
+        _tail_tensor(thr_index, "thr_index", torch.int32, (K,))
+    _tail_tensor(fleet_sums, "fleet_sums", torch.int64, (2,))
+    if out is None:
+        out = TailScores(torch.empty(R, dtype=torch.float64, device=d),
+                         torch.empty(R, dtype=torch.int64, device=d),
+                         torch.empty(R, dtype=torch.int64, device=d),
+                         torch.empty(R, dtype=torch.uint8, device=d))
+    _tail_tensor(out.score, "out.score", torch.float64, (R,))
+    _tail_tensor(out.tail_ns, "out.tail_ns", torch.int64, (R,))
+    _tail_tensor(out.total_ns, "out.total_ns", torch.int64, (R,))
+    if out.strag is not None:
+        _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
+    calls = None
+    if tail_calls is True:
+        calls = out.tail_calls
+        if calls is None:
+            calls = torch.empty((R, K), dtype=torch.int32, device=d)
+    elif tail_calls is not False and tail_calls is not None:
+        calls = tail_calls
+    if calls is not None:
+        _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
+    a = N.SegTailArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
+                      int(aligned16), thr.data_ptr(), N.ptr(thr_index), fleet_sums.data_ptr(),
+                      out.tail_ns.data_ptr(), out.total_ns.data_ptr(), out.score.data_ptr(),
+                      N.ptr(calls), N.ptr(out.strag), float(score_thr))
+    N.call("nvrx_segment_tail_scores_ragged", ctypes.byref(a), _stream(stream))
+    return TailScores(out.score, out.tail_ns, out.total_ns, out.strag, calls)
+
+
 @dataclass
 class HistoryTailScores:
     """Per row of ``histogram_history_scores`` (device tensors): score [R] float64, tail_ns /
