@@ -32,7 +32,7 @@
  * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms,
  * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores,
  * nvrx_histogram_tail_base / _tail_attribution, nvrx_segment_fleet_histogram_ragged,
- * nvrx_segment_tail_scores_ragged.
+ * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -467,6 +467,47 @@ typedef struct nvrx_tailattr_args {
 int nvrx_histogram_tail_base(const uint64_t* fleet, int64_t K, const int32_t* thr, uint64_t* base,
                              void* stream);
 int nvrx_histogram_tail_attribution(const nvrx_tailattr_args* args, void* stream);
+
+/* The relative tail score attribution straight from ragged segments, without the counts matrix: the
+ * step after nvrx_segment_tail_scores_ragged.  No reference counterpart.  Segments, max_len, cap
+ * and aligned16 as in "The same tail scores straight from ragged segments" above; thr, thr_index,
+ * base and every output as in "Tail score attribution" above.  By definition
+ *   nvrx_segment_tail_attribution_ragged  writes into idx, loss, tail_ns, total_ns, tail_calls,
+ *     thr_bucket, base_share ([R][top]) and loss_all ([R][K], written in full) what is equal to
+ *     nvrx_histogram_tail_attribution with kind = NVRX_ATTR_RELATIVE applied to the counts
+ *     nvrx_segment_histogram_ragged would write into a zeroed matrix for the same segments:
+ *     an element (r, k) is taken iff u >= 0, thr[u] >= 0, its retained length is > 0 and its loss
+ *     is not NaN; tail, total (u64 mod 2^64) and calls (u32) are sums of w(bucket(x)) / 1 over the
+ *     retained samples x, tail and calls over bucket(x) > thr[u] only.
+ * base[u] = {btail, btotal} comes from nvrx_histogram_tail_base on the fleet of
+ * nvrx_segment_fleet_histogram_ragged and the thr of nvrx_histogram_tail_threshold.  Every sum is
+ * an exact integer, so the results equal the dense chain's bit for bit and are identical from run
+ * to run.  seg_off, base, loss, tail_ns, total_ns, base_share and loss_all 8-byte aligned; top in
+ * 1..NVRX_MAX_ATTRIBUTION; K * 240 and R * K below 2^31; the retained run at most
+ * NVRX_MAX_SEGMENT.  R == 0 or K == 0 launches nothing (outputs untouched).  Two kernels on
+ * `stream` only (every (r, k) has one owner): no allocation, no synchronisation, no host
+ * read-back, no scratch, no atomics; capturable as a linear chain with the calls before it. */
+typedef struct nvrx_segtailattr_args {
+    int64_t R, K;
+    const uint32_t* ns;         /* duration keys */
+    const int64_t* seg_off;     /* [R * K] (+ 1 without seg_len) */
+    const int32_t* seg_len;     /* [R * K] or NULL */
+    int64_t max_len, cap;
+    int32_t aligned16;          /* the caller's word that every retained run starts 16-byte aligned */
+    int32_t top;                /* 1..NVRX_MAX_ATTRIBUTION */
+    const int32_t* thr;         /* threshold buckets, from nvrx_histogram_tail_threshold */
+    const int32_t* thr_index;   /* [K] or NULL */
+    const uint64_t* base;       /* [.][2] {btail, btotal}, from nvrx_histogram_tail_base */
+    int32_t* idx;               /* [R][top] */
+    double* loss;               /* [R][top] */
+    uint64_t* tail_ns;          /* [R][top] */
+    uint64_t* total_ns;         /* [R][top] */
+    uint32_t* tail_calls;       /* [R][top] */
+    int32_t* thr_bucket;        /* [R][top] */
+    double* base_share;         /* [R][top] */
+    double* loss_all;           /* [R][K] */
+} nvrx_segtailattr_args;
+int nvrx_segment_tail_attribution_ragged(const nvrx_segtailattr_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

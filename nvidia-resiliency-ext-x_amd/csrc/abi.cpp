@@ -5,7 +5,8 @@
 // code + thread-local message.  The profiler handle that replaces the reference's
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
-// histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip and records.hip.
+// histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip,
+// segment_tail_attribution.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -418,6 +419,38 @@ int nvrx_segment_tail_scores_ragged(const nvrx_segtail_args* a, void* stream) {
     NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
     return hip_status(nvrx::segment_tail_scores_ragged(*a, S(stream)), fn.c_str());
+}
+
+// the relative tail score attribution straight from those segments (segment_tail_attribution.hip)
+int nvrx_segment_tail_attribution_ragged(const nvrx_segtailattr_args* a, void* stream) {
+    const std::string fn("nvrx_segment_tail_attribution_ragged");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
+                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
+                              a->max_len, a->cap))
+        return rc;
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->thr, fn + ": null thr");
+        NVRX_CHECK_ARG(a->base, fn + ": null base");
+        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
+        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
+        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
+        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
+        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
+        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->base & 7) == 0, fn + ": base not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
+    return hip_status(nvrx::segment_tail_attribution_ragged(*a, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

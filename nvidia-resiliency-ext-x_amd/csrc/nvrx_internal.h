@@ -58,6 +58,8 @@ hipError_t segment_fleet_histogram_ragged(const uint32_t* ns, const int64_t* seg
                                           const int32_t* seg_len, int64_t R, int64_t K, int64_t max_len,
                                           int64_t cap, int accumulate, uint64_t* fleet, hipStream_t st);
 hipError_t segment_tail_scores_ragged(const nvrx_segtail_args& a, hipStream_t st);
+// the relative tail score attribution straight from those segments (segment_tail_attribution.hip)
+hipError_t segment_tail_attribution_ragged(const nvrx_segtailattr_args& a, hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

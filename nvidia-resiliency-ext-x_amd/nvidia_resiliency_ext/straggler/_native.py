@@ -107,6 +107,15 @@ class TailAttrArgs(ctypes.Structure):
     ]
 
 
+class SegTailAttrArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("ns", P), ("seg_off", P), ("seg_len", P), ("max_len", i64),
+        ("cap", i64), ("aligned16", i32), ("top", i32), ("thr", P), ("thr_index", P), ("base", P),
+        ("idx", P), ("loss", P), ("tail_ns", P), ("total_ns", P), ("tail_calls", P),
+        ("thr_bucket", P), ("base_share", P), ("loss_all", P),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -156,6 +165,7 @@ SIGNATURES = {
     "nvrx_histogram_tail_attribution": (ctypes.c_int, [ctypes.POINTER(TailAttrArgs), P]),
     "nvrx_segment_fleet_histogram_ragged": (ctypes.c_int, [P, P, P, i64, i64, i64, i64, i32, i32, P, P]),
     "nvrx_segment_tail_scores_ragged": (ctypes.c_int, [ctypes.POINTER(SegTailArgs), P]),
+    "nvrx_segment_tail_attribution_ragged": (ctypes.c_int, [ctypes.POINTER(SegTailAttrArgs), P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

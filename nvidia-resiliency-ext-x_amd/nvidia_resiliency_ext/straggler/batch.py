@@ -482,8 +482,8 @@ class MatrixReporter:
                                if top else None)
 
     def tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor, permille: int = 990,
-                            threshold: Optional[float] = None,
-                            tail_calls: bool = False) -> BatchTailScores:
+                            threshold: Optional[float] = None, tail_calls: bool = False,
+                            attribute: int = 0) -> BatchTailScores:
         """The tail scores of ``tail_scores`` for the record streams ``report_records`` takes
         (recs [n, 2] int32 {slot, ns}, rec_off [R + 1] int64, device), over the windows that
         report retains (the last ``cap`` records of every rank and kernel) -- without the
@@ -494,8 +494,15 @@ class MatrixReporter:
         counts of those buckets (``histograms.segment_tail_scores`` on the host).  It queues
         behind reports in flight and touches none of the report's buffers: the bucketing goes
         into work tensors of its own, allocated at first use and grown on demand; the results
-        come in one device-to-host copy.  ``.attribution`` stays None.  Beyond the reference."""
+        come in one device-to-host copy.  ``attribute=top`` (1..16) adds ``.attribution`` as
+        ``tail_scores(attribute=)`` does -- per rank the `top` kernels with the largest excess tail
+        time, ``histograms.segment_tail_attribution`` on the host -- again without the counts:
+        ``ops.histogram_tail_base`` on the call's fleet, then
+        ``ops.segment_tail_attribution_ragged`` on the call's own buckets, packed behind the
+        call's outputs in the same device-to-host copy; its buffers are allocated once per
+        reporter.  Without it ``.attribution`` stays None.  Beyond the reference."""
         pm = ops.tail_permille(permille)
+        top = ops.attribution_request(attribute, "relative")[0] if attribute else 0
         if self.exchange:
             raise NotImplementedError("MatrixReporter.tail_scores_records: tail scores across "
                                       "kernel shards (exchange=True) are not supported")
@@ -520,6 +527,11 @@ class MatrixReporter:
                            torch.empty(max(need, 1), dtype=torch.int32, device=d),
                            torch.empty(R * K, dtype=torch.int32, device=d))
         base_len = buf.numel()
+        if top:  # the same layout at the head of a longer buffer
+            aoff = self._tail_attr_buffers(t, base_len)
+            if t.get("base") is None:
+                t["base"] = torch.empty((K, 2), dtype=torch.int64, device=d)
+            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
         i64 = buf[:8 * (3 * R + 2)].view(torch.int64)
         thr = buf[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(torch.int32)[:K]
         sums = i64[3 * R:]
@@ -539,6 +551,11 @@ class MatrixReporter:
             out_ns, seg_off, seg_len, K, max_len, thr, sums, aligned16=True, out=out,
             score_thr=self.thr_rel if threshold is None else threshold,
             tail_calls=t["calls"] if tail_calls else False)
+        if top:
+            ops.histogram_tail_base(t["fleet"], thr, out=t["base"])
+            ops.segment_tail_attribution_ragged(
+                out_ns, seg_off, seg_len, K, max_len, thr, t["base"], top=top, aligned16=True,
+                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
         h64 = host[:8 * (3 * R + 2)].view(np.uint64)
         ftail, ftotal = int(h64[3 * R]), int(h64[3 * R + 1])
@@ -547,7 +564,9 @@ class MatrixReporter:
                                float(ftail) / float(ftotal) if ftotal else float("nan"),
                                host[8 * (3 * R + 2) + 4 * kp:base_len].astype(bool),
                                host[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(np.int32)[:K].copy(),
-                               res.tail_calls, None)
+                               res.tail_calls,
+                               BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
+                               if top else None)
 
     def individual_tail_scores(self, counts: torch.Tensor, permille: int = 990,
                                threshold: Optional[float] = None, absorb: str = "healthy",

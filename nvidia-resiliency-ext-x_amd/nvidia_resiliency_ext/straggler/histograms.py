@@ -27,7 +27,9 @@ interval against its own summed history, and the history with the interval folde
 the largest excess tail time in ns.
 ``segment_counts`` / ``segment_tail_scores`` are the host twins of the tail scores taken straight
 from ragged segments, without the counts (``ops.segment_fleet_histogram_ragged``,
-``ops.segment_tail_scores_ragged``, ``MatrixReporter.tail_scores_records``).
+``ops.segment_tail_scores_ragged``, ``MatrixReporter.tail_scores_records``), and
+``segment_tail_attribution`` of their attribution (``ops.segment_tail_attribution_ragged``,
+``MatrixReporter.tail_scores_records(attribute=)``).
 """
 from __future__ import annotations
 
@@ -461,6 +463,17 @@ def history_attribution(counts, hist, permille: int, top: int, hist_index=None,
         return loss, tail, total, calls, t, share
 
     return _attribution(R, K, top, element)
+
+
+def segment_tail_attribution(keys, seg_off, seg_len, K: int, permille: int, top: int, cap: int = 0,
+                             col_valid=None, thr_index=None) -> TailAttribution:
+    """The kernels behind the tail score of each row straight from ragged segments of duration
+    keys (``segment_counts``'s addressing), the host twin of ``ops.segment_fleet_histogram_ragged``
+    -> ``histogram_tail_threshold`` -> ``histogram_tail_base`` ->
+    ``segment_tail_attribution_ragged`` and of ``MatrixReporter.tail_scores_records(attribute=)``:
+    ``tail_attribution`` over the retained windows' counts, the fleet being their sum over rows."""
+    return tail_attribution(segment_counts(keys, seg_off, seg_len, K, cap), permille, top, col_valid,
+                            thr_index=thr_index)
 
 
 def quantile_bounds(counts, permille: int):

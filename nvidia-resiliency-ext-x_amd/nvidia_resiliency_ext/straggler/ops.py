@@ -699,6 +699,48 @@ def histogram_tail_attribution(counts: torch.Tensor, *, top: int, kind: str,
     return out
 
 
+def segment_tail_attribution_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
+                                    seg_len: Optional[torch.Tensor], K: int, max_len: int,
+                                    thr: torch.Tensor, base: torch.Tensor, *, top: int,
+                                    cap: int = 0, aligned16: bool = False,
+                                    thr_index: Optional[torch.Tensor] = None,
+                                    out: Optional[TailAttribution] = None,
+                                    stream=None) -> TailAttribution:
+    """The kernels behind a tail score straight from the ragged segments (segment r * K + k: row
+    r, kernel k), equal to ``histogram_tail_attribution(kind="relative")`` on the counts
+    ``segment_histogram_ragged`` would write into a zeroed [R, K, 240] tensor: ``thr`` (int32,
+    ``histogram_tail_threshold`` on the fleet of ``segment_fleet_histogram_ragged``), ``base``
+    (int64 [., 2], ``histogram_tail_base``), ``thr_index``, ``top`` and ``out`` as there.  Two
+    launches, no scratch; ``out.loss_all`` is also the workspace."""
+    top, _ = attribution_request(top, "relative")
+    R = _segment_rows(ns, seg_off, seg_len, K)
+    d = ns.device
+    N.require_device(thr, "thr")
+    if thr.dtype != torch.int32 or thr.dim() != 1 or not thr.is_contiguous():
+        raise ValueError("thr must be a contiguous int32 tensor")
+    _tail_tensor(base, "base", torch.int64, (thr.numel(), 2))
+    if thr_index is None:
+        if thr.numel() != K:
+            raise ValueError("thr must hold K entries (or pass thr_index)")
+    else:
+        _tail_tensor(thr_index, "thr_index", torch.int32, (K,))
+    if out is None:
+        out = TailAttribution.empty(R, K, top, d)
+    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
+                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
+                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
+        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
+    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    a = N.SegTailAttrArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
+                          int(aligned16), top, thr.data_ptr(), N.ptr(thr_index), base.data_ptr(),
+                          out.idx.data_ptr(), out.loss.data_ptr(), out.tail_ns.data_ptr(),
+                          out.total_ns.data_ptr(), out.tail_calls.data_ptr(),
+                          out.thr_bucket.data_ptr(), out.base_share.data_ptr(),
+                          out.loss_all.data_ptr())
+    N.call("nvrx_segment_tail_attribution_ragged", ctypes.byref(a), _stream(stream))
+    return out
+
+
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,
                scratch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """ref[k] = min_r med[r, k] if every row has k (num > 0), else NaN (reporting.py:255-296)."""
