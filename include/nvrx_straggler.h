@@ -32,7 +32,8 @@
  * nvrx_histogram_bucket / _edge, nvrx_segment_histogram_*, nvrx_profiler_get_histograms,
  * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores,
  * nvrx_histogram_tail_base / _tail_attribution, nvrx_segment_fleet_histogram_ragged,
- * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged.
+ * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged,
+ * nvrx_segment_history_scores_ragged.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -401,6 +402,55 @@ typedef struct nvrx_histtail_args {
     uint32_t* tail_calls;       /* [R][K] or NULL */
 } nvrx_histtail_args;
 int nvrx_histogram_history_scores(const nvrx_histtail_args* args, void* stream);
+
+/* The same individual tail scores straight from ragged segments, without the counts matrix: the
+ * individual leg for a fleet that arrives as record streams.  No reference counterpart.  Segments,
+ * max_len, cap and aligned16 as in "The same tail scores straight from ragged segments" above:
+ * segment r * K + k is row r, kernel k; the last min(len, cap) samples are retained; seg_len[s] <= 0
+ * is an empty element; seg_len NULL: seg_off holds R * K + 1 offsets.  By definition
+ *   nvrx_segment_history_scores_ragged  writes into tail_ns, total_ns, base_tail_ns, base_total_ns,
+ *     score, strag and tail_calls, and changes in hist, exactly what nvrx_histogram_history_scores
+ *     does for the same hist, hist_stride, hist_index, col_valid, skip_rows, permille, mode and
+ *     score_thr applied to the counts nvrx_segment_histogram_ragged would write into a zeroed
+ *     matrix for the same segments.
+ * "n > 0" of that definition is "retained length > 0".  An empty element is therefore not eligible,
+ * leaves its history slot bit-identical under UPDATE and gives tail_calls = 0; its history is not
+ * read.  total, tail (u64 mod 2^64) and calls (u32) are sums of w(bucket(x)) / 1 over the retained
+ * samples x; UPDATE adds, saturating, only to the bins the samples fall in.  SCORE, UPDATE and both
+ * as there: with both bits the score sees the history from before the call; skip_rows may be the
+ * strag a previous call wrote on the device; tail_calls ([R][K] or NULL) is written in full and
+ * ignored without SCORE.  The history keeps its format, so one history can be continued by either
+ * entry.  Every sum is an exact integer: the results equal the dense chain's bit for bit and are
+ * identical from run to run.  hist 16-byte aligned; seg_off and the four u64 outputs 8-byte
+ * aligned; mode needs at least one bit; permille in 0..1000; the retained run at most
+ * NVRX_MAX_SEGMENT; K * 240 and R * K below 2^31.  R == 0 or K == 0 launches nothing.
+ * Stream-ordered: kernels on `stream` only, no allocation, no synchronisation, no host read-back,
+ * no scratch; capturable as a linear chain.  The four u64 outputs are the accumulators of the pass
+ * (cleared on the stream first): they must not alias. */
+typedef struct nvrx_seghist_args {
+    int64_t R, K;
+    const uint32_t* ns;         /* duration keys */
+    const int64_t* seg_off;     /* [R * K] (+ 1 without seg_len) */
+    const int32_t* seg_len;     /* [R * K] or NULL */
+    int64_t max_len, cap;
+    int32_t aligned16;          /* the caller's word that every retained run starts 16-byte aligned */
+    uint32_t* hist;             /* [R][hist_stride][NVRX_HIST_BINS], in place */
+    int64_t hist_stride;        /* in histograms; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* [K] or NULL */
+    const uint8_t* skip_rows;   /* [R] or NULL */
+    int32_t permille;
+    int32_t mode;               /* NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE */
+    double score_thr;
+    uint64_t* tail_ns;          /* [R] */
+    uint64_t* total_ns;         /* [R] */
+    uint64_t* base_tail_ns;     /* [R] */
+    uint64_t* base_total_ns;    /* [R] */
+    double* score;              /* [R] */
+    uint8_t* strag;             /* [R] or NULL */
+    uint32_t* tail_calls;       /* [R][K] or NULL */
+} nvrx_seghist_args;
+int nvrx_segment_history_scores_ragged(const nvrx_seghist_args* args, void* stream);
 
 /* Tail score attribution: the kernels behind a rank's tail score.  No reference counterpart.  The
  * tail scores above flag a row that is slow on every n-th call; this names the kernels, per row

@@ -6,7 +6,7 @@
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
 // histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip,
-// segment_tail_attribution.hip and records.hip.
+// segment_tail_attribution.hip, segment_history.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -451,6 +451,46 @@ int nvrx_segment_tail_attribution_ragged(const nvrx_segtailattr_args* a, void* s
     NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
     return hip_status(nvrx::segment_tail_attribution_ragged(*a, S(stream)), fn.c_str());
+}
+
+// the individual tail scores straight from those segments (segment_history.hip)
+int nvrx_segment_history_scores_ragged(const nvrx_seghist_args* a, void* stream) {
+    const std::string fn("nvrx_segment_history_scores_ragged");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
+                              a->max_len, a->cap))
+        return rc;
+    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
+                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
+    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                   fn + ": hist_stride below K without hist_index");
+    const bool score = a->mode & NVRX_HTAIL_SCORE;
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->hist, fn + ": null hist");
+        if (score) {
+            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
+            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
+            NVRX_CHECK_ARG(a->score, fn + ": null score");
+        }
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
+    if (score) {
+        NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->base_tail_ns & 7) == 0, fn + ": base_tail_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->base_total_ns & 7) == 0,
+                       fn + ": base_total_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
+    }
+    nvrx_seghist_args b = *a;
+    if (!score) b.tail_calls = nullptr;  // ignored without SCORE
+    return hip_status(nvrx::segment_history_scores_ragged(b, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

@@ -481,6 +481,38 @@ class MatrixReporter:
                                BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
                                if top else None)
 
+    def _records_tail_work(self, n: int) -> dict:
+        """The tail work tensors of the record-stream methods (``tail_scores_records``,
+        ``individual_tail_scores_records``), allocated at first use, the bucketing scratch grown to
+        hold ``n`` records."""
+        R, K, d = self.R, self.K, self.device
+        if self._rtail is None:
+            # packed as tail_scores packs:
+            # [score f64 R][tail_ns i64 R][total_ns i64 R][fleet_sums i64 2][thr i32 K+pad][strag u8 R]
+            kp = (K + 1) // 2 * 2
+            self._rtail = dict(buf=torch.zeros(8 * (3 * R + 2) + 4 * kp + R, dtype=torch.uint8, device=d),
+                               fleet=torch.empty((K, histograms.BINS), dtype=torch.int64, device=d),
+                               calls=None, kp=kp, bucket=None)
+        t = self._rtail
+        need = ops.records_bucket_capacity(n, R, K)
+        if t["bucket"] is None or t["bucket"][2].numel() < need:
+            t["bucket"] = (torch.empty(R * K, dtype=torch.int64, device=d),
+                           torch.empty(R * K, dtype=torch.int32, device=d),
+                           torch.empty(max(need, 1), dtype=torch.int32, device=d),
+                           torch.empty(R * K, dtype=torch.int32, device=d))
+        return t
+
+    def _history_tail_work(self) -> dict:
+        """The history and packed outputs of the individual tail scores (both methods continue the
+        one history), allocated at first use."""
+        if self._htail is None:
+            R, K, d = self.R, self.K, self.device
+            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns i64 R][strag u8 R]
+            self._htail = dict(buf=torch.zeros(41 * R, dtype=torch.uint8, device=d),
+                               hist=torch.zeros((R, K, histograms.BINS), dtype=torch.int32, device=d),
+                               calls=None)
+        return self._htail
+
     def tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor, permille: int = 990,
                             threshold: Optional[float] = None, tail_calls: bool = False,
                             attribute: int = 0) -> BatchTailScores:
@@ -510,22 +542,9 @@ class MatrixReporter:
         if rec_off.numel() != R + 1:
             raise ValueError(f"rec_off must hold {R + 1} offsets")
         self._order_after_inflight()
-        if self._rtail is None:
-            # packed as tail_scores packs:
-            # [score f64 R][tail_ns i64 R][total_ns i64 R][fleet_sums i64 2][thr i32 K+pad][strag u8 R]
-            kp = (K + 1) // 2 * 2
-            self._rtail = dict(buf=torch.zeros(8 * (3 * R + 2) + 4 * kp + R, dtype=torch.uint8, device=d),
-                               fleet=torch.empty((K, histograms.BINS), dtype=torch.int64, device=d),
-                               calls=None, kp=kp, bucket=None)
-        t = self._rtail
+        t = self._records_tail_work(recs.shape[0])
         kp, buf = t["kp"], t["buf"]
         n = recs.shape[0]
-        need = ops.records_bucket_capacity(n, R, K)
-        if t["bucket"] is None or t["bucket"][2].numel() < need:
-            t["bucket"] = (torch.empty(R * K, dtype=torch.int64, device=d),
-                           torch.empty(R * K, dtype=torch.int32, device=d),
-                           torch.empty(max(need, 1), dtype=torch.int32, device=d),
-                           torch.empty(R * K, dtype=torch.int32, device=d))
         base_len = buf.numel()
         if top:  # the same layout at the head of a longer buffer
             aoff = self._tail_attr_buffers(t, base_len)
@@ -612,12 +631,7 @@ class MatrixReporter:
         if tuple(counts.shape) != (R, K, histograms.BINS):
             raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
         self._order_after_inflight()
-        if self._htail is None:
-            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns i64 R][strag u8 R]
-            self._htail = dict(buf=torch.zeros(41 * R, dtype=torch.uint8, device=d),
-                               hist=torch.zeros((R, K, histograms.BINS), dtype=torch.int32, device=d),
-                               calls=None)
-        t = self._htail
+        t = self._history_tail_work()
         buf = t["buf"]
         if top:  # the same layout at the head of a longer buffer
             aoff = self._tail_attr_buffers(t, 41 * R)
@@ -651,6 +665,66 @@ class MatrixReporter:
                                          res.tail_calls,
                                          BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
                                          if top else None)
+
+    def individual_tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor,
+                                       permille: int = 990, threshold: Optional[float] = None,
+                                       absorb: str = "healthy",
+                                       tail_calls: bool = False) -> BatchIndividualTailScores:
+        """The individual tail scores of ``individual_tail_scores`` for the record streams
+        ``report_records`` takes (recs [n, 2] int32 {slot, ns}, rec_off [R + 1] int64, device),
+        over the windows that report retains (the last ``cap`` records of every rank and kernel)
+        -- without the [R, K, 240] counts of the interval.  The streams are bucketed with every
+        bucket written out into the work tensors ``tail_scores_records`` uses, then
+        ``ops.segment_history_scores_ragged`` scores the buckets against, and folds them into, the
+        SAME history ``individual_tail_scores`` keeps: the two methods continue one history
+        (``reset_tail_history`` clears it), and the results are, bit for bit, what
+        ``individual_tail_scores`` gives on the histograms of those buckets
+        (``histograms.segment_history_scores`` on the host).  A (rank, kernel) without records in
+        the interval is not scored and leaves its history as it is.  ``absorb`` as there:
+        ``"healthy"`` -- a score launch, then an update launch that skips the flagged ranks on the
+        device; ``"always"`` -- one fused launch; ``"never"`` -- score only.  It queues behind
+        reports in flight and touches none of the report's buffers; the results come in one
+        device-to-host copy; ``.attribution`` is None (the individual attribution for record
+        streams is not built).  Beyond the reference."""
+        pm = ops.tail_permille(permille)
+        if absorb not in ABSORB_MODES:
+            raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.individual_tail_scores_records: tail scores "
+                                      "across kernel shards (exchange=True) are not supported")
+        R, K, d = self.R, self.K, self.device
+        if rec_off.numel() != R + 1:
+            raise ValueError(f"rec_off must hold {R + 1} offsets")
+        self._order_after_inflight()
+        n = recs.shape[0]
+        w = self._records_tail_work(n)
+        t = self._history_tail_work()
+        buf = t["buf"]
+        i64 = buf[:40 * R].view(torch.int64)
+        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
+                                    i64[3 * R:4 * R], i64[4 * R:], buf[40 * R:41 * R])
+        if tail_calls and t["calls"] is None:
+            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
+        # as tail_scores_records: every bucket written out, trimmed to `cap`, starts padded to 16 bytes
+        seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=w["bucket"])
+        max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
+        res = ops.segment_history_scores_ragged(
+            out_ns, seg_off, seg_len, K, max_len, t["hist"], permille=pm, update=absorb == "always",
+            aligned16=True, col_valid=self.col_valid,
+            score_thr=self.thr_ind if threshold is None else threshold,
+            tail_calls=t["calls"] if tail_calls else False, out=out)
+        if absorb == "healthy":
+            ops.segment_history_scores_ragged(out_ns, seg_off, seg_len, K, max_len, t["hist"],
+                                              permille=pm, score=False, aligned16=True,
+                                              col_valid=self.col_valid, skip_rows=out.strag)
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        h64 = host[:40 * R].view(np.uint64).reshape(5, R).copy()
+        btail, btotal = h64[3], h64[4]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
+        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
+                                         host[40 * R:41 * R].astype(bool), btail, btotal,
+                                         res.tail_calls, None)
 
     def reset_tail_history(self) -> None:
         """Forget the history of ``individual_tail_scores``: the next interval scores NaN."""

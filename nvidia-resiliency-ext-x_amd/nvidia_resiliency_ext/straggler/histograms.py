@@ -316,6 +316,15 @@ def history_scores(counts, hist, permille: int, *, score: bool = True, update: b
     return res
 
 
+def segment_history_scores(keys, seg_off, seg_len, K: int, hist, permille: int, cap: int = 0,
+                           **kwargs) -> HistoryScores:
+    """Individual tail score per row straight from ragged segments of duration keys
+    (``segment_counts``'s addressing) against the rows' own history, the host twin of
+    ``ops.segment_history_scores_ragged`` and of ``MatrixReporter.individual_tail_scores_records``:
+    ``history_scores`` (its keywords pass through) over the retained windows' counts."""
+    return history_scores(segment_counts(keys, seg_off, seg_len, K, cap), hist, permille, **kwargs)
+
+
 @dataclass
 class TailAttribution:
     """``tail_attribution`` / ``history_attribution``: per row the ``top`` kernels with the largest

@@ -561,6 +561,68 @@ def histogram_history_scores(counts: torch.Tensor, hist: torch.Tensor, *, permil
                              out.base_total_ns, out.strag, calls)
 
 
+def segment_history_scores_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
+                                  seg_len: Optional[torch.Tensor], K: int, max_len: int,
+                                  hist: torch.Tensor, *, permille: int, score: bool = True,
+                                  update: bool = True, cap: int = 0, aligned16: bool = False,
+                                  hist_index: Optional[torch.Tensor] = None, hist_stride: int = 0,
+                                  col_valid: Optional[torch.Tensor] = None,
+                                  skip_rows: Optional[torch.Tensor] = None, score_thr: float = 0.75,
+                                  tail_calls=False, out: Optional[HistoryTailScores] = None,
+                                  stream=None) -> HistoryTailScores:
+    """Individual tail score per row straight from the ragged segments (segment r * K + k: row r,
+    kernel k; the last ``cap`` samples retained, a length <= 0 an empty element) against the row's
+    own history ``hist``: what ``histogram_history_scores`` gives, and does to ``hist``, on the
+    counts ``segment_histogram_ragged`` would write into a zeroed [R, K, 240] tensor -- without
+    that tensor.  An element without retained samples is not scored and leaves its history slot as
+    it is.  ``hist`` keeps its format, so one history can be continued by either function; every
+    other argument and ``out`` as in ``histogram_history_scores``."""
+    pm = tail_permille(permille)
+    if not (score or update):
+        raise ValueError("segment_history_scores_ragged: at least one of score and update")
+    R = _segment_rows(ns, seg_off, seg_len, K)
+    d = ns.device
+    stride = int(hist_stride)
+    if stride < 0 or (stride and hist_index is None and stride < K):
+        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
+    N.require_device(hist, "hist")
+    if hist.dtype not in (torch.int32, torch.uint32) or hist.data_ptr() % 16:
+        raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
+    _tail_tensor(hist, "hist", hist.dtype, (R, stride or K, N.HIST_BINS))
+    if hist_index is not None:
+        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
+    _u8_vector(col_valid, "col_valid", K)
+    _u8_vector(skip_rows, "skip_rows", R)
+    calls = None
+    if score:
+        if out is None:
+            out = HistoryTailScores.empty(R, d)
+        _tail_tensor(out.score, "out.score", torch.float64, (R,))
+        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
+            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
+        if out.strag is not None:
+            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
+        if tail_calls is True:
+            calls = out.tail_calls
+            if calls is None:
+                calls = torch.empty((R, K), dtype=torch.int32, device=d)
+        elif tail_calls is not False and tail_calls is not None:
+            calls = tail_calls
+        if calls is not None:
+            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
+    elif out is None:
+        out = HistoryTailScores()
+    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    a = N.SegHistArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
+                      int(aligned16), hist.data_ptr(), stride, N.ptr(hist_index), N.ptr(col_valid),
+                      N.ptr(skip_rows), pm, mode, float(score_thr), N.ptr(out.tail_ns),
+                      N.ptr(out.total_ns), N.ptr(out.base_tail_ns), N.ptr(out.base_total_ns),
+                      N.ptr(out.score), N.ptr(out.strag), N.ptr(calls))
+    N.call("nvrx_segment_history_scores_ragged", ctypes.byref(a), _stream(stream))
+    return HistoryTailScores(out.score, out.tail_ns, out.total_ns, out.base_tail_ns,
+                             out.base_total_ns, out.strag, calls)
+
+
 def histogram_tail_base(fleet: torch.Tensor, thr: torch.Tensor, out: Optional[torch.Tensor] = None,
                         stream=None) -> torch.Tensor:
     """Per kernel of a fleet histogram (int64 [K, 240]) its weighted {tail, total} ns over the
