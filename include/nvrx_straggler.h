@@ -33,7 +33,7 @@
  * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores,
  * nvrx_histogram_tail_base / _tail_attribution, nvrx_segment_fleet_histogram_ragged,
  * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged,
- * nvrx_segment_history_scores_ragged.
+ * nvrx_segment_history_scores_ragged, nvrx_segment_history_attribution_ragged.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -558,6 +558,58 @@ typedef struct nvrx_segtailattr_args {
     double* loss_all;           /* [R][K] */
 } nvrx_segtailattr_args;
 int nvrx_segment_tail_attribution_ragged(const nvrx_segtailattr_args* args, void* stream);
+
+/* The individual tail score attribution straight from ragged segments, without the counts matrix:
+ * the step after (or between the two launches of) nvrx_segment_history_scores_ragged.  No reference
+ * counterpart.  Segments, max_len, cap and aligned16 as in "The same tail scores straight from
+ * ragged segments" above; hist, hist_stride, hist_index, col_valid and permille as in
+ * nvrx_segment_history_scores_ragged; every output as in "Tail score attribution" above.  By
+ * definition
+ *   nvrx_segment_history_attribution_ragged  writes into idx, loss, tail_ns, total_ns, tail_calls,
+ *     thr_bucket, base_share ([R][top]) and loss_all ([R][K], written in full) what is equal, bit
+ *     for bit, to nvrx_histogram_tail_attribution with kind = NVRX_ATTR_INDIVIDUAL for the same
+ *     hist, hist_stride, hist_index, col_valid, permille and top applied to the counts
+ *     nvrx_segment_histogram_ragged would write into a zeroed matrix for the same segments:
+ *     an element (r, k) is taken iff col_valid[k] != 0, its slot s >= 0, the history has N > 0, its
+ *     retained length is > 0 and its loss is not NaN; tail, total (u64 mod 2^64) and calls (u32)
+ *     are sums of w(bucket(x)) / 1 over the retained samples x, tail and calls over bucket(x) > T
+ *     only; T, btail and btotal come from H[r][s] by the rank rule of
+ *     nvrx_histogram_history_scores; share = btail / btotal and loss = tail - total * share are
+ *     three separately rounded f64 operations; ties go to the lower column, -0.0 == +0.0; beyond
+ *     the taken elements the outputs are -1 / NaN / 0.
+ * hist is READ ONLY here: run the entry between a SCORE call and an UPDATE call and it sees the
+ * history the score saw.  An empty element (seg_len <= 0) gets NaN in loss_all, and its 960 B of
+ * history are not read.  Every sum is an exact integer, so the results equal the dense chain's bit
+ * for bit and are identical from run to run.  hist 16-byte aligned; seg_off, loss, tail_ns,
+ * total_ns, base_share and loss_all 8-byte aligned; top in 1..NVRX_MAX_ATTRIBUTION; permille in
+ * 0..1000; hist_stride 0 or, without hist_index, at least K; the retained run at most
+ * NVRX_MAX_SEGMENT; K * 240 and R * K below 2^31.  R == 0 or K == 0 launches nothing (outputs
+ * untouched).  Two kernels on `stream` only (every (r, k) has one owner): no allocation, no
+ * synchronisation, no host read-back, no scratch, no atomics; capturable as a linear chain with
+ * the calls around it. */
+typedef struct nvrx_seghistattr_args {
+    int64_t R, K;
+    const uint32_t* ns;         /* duration keys */
+    const int64_t* seg_off;     /* [R * K] (+ 1 without seg_len) */
+    const int32_t* seg_len;     /* [R * K] or NULL */
+    int64_t max_len, cap;
+    int32_t aligned16;          /* the caller's word that every retained run starts 16-byte aligned */
+    int32_t top;                /* 1..NVRX_MAX_ATTRIBUTION */
+    const uint32_t* hist;       /* [R][hist_stride][NVRX_HIST_BINS], read only */
+    int64_t hist_stride;        /* in histograms; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* [K] or NULL */
+    int32_t permille;
+    int32_t* idx;               /* [R][top] */
+    double* loss;               /* [R][top] */
+    uint64_t* tail_ns;          /* [R][top] */
+    uint64_t* total_ns;         /* [R][top] */
+    uint32_t* tail_calls;       /* [R][top] */
+    int32_t* thr_bucket;        /* [R][top] */
+    double* base_share;         /* [R][top] */
+    double* loss_all;           /* [R][K] */
+} nvrx_seghistattr_args;
+int nvrx_segment_history_attribution_ragged(const nvrx_seghistattr_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

@@ -6,7 +6,8 @@
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
 // histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip,
-// segment_tail_attribution.hip, segment_history.hip and records.hip.
+// segment_tail_attribution.hip, segment_history.hip, segment_history_attribution.hip and
+// records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -491,6 +492,42 @@ int nvrx_segment_history_scores_ragged(const nvrx_seghist_args* a, void* stream)
     nvrx_seghist_args b = *a;
     if (!score) b.tail_calls = nullptr;  // ignored without SCORE
     return hip_status(nvrx::segment_history_scores_ragged(b, S(stream)), fn.c_str());
+}
+
+// the individual tail score attribution straight from those segments
+// (segment_history_attribution.hip)
+int nvrx_segment_history_attribution_ragged(const nvrx_seghistattr_args* a, void* stream) {
+    const std::string fn("nvrx_segment_history_attribution_ragged");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
+                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
+                              a->max_len, a->cap))
+        return rc;
+    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                   fn + ": hist_stride below K without hist_index");
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->hist, fn + ": null hist");
+        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
+        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
+        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
+        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
+        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
+        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
+    return hip_status(nvrx::segment_history_attribution_ragged(*a, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

@@ -62,6 +62,8 @@ hipError_t segment_tail_scores_ragged(const nvrx_segtail_args& a, hipStream_t st
 hipError_t segment_tail_attribution_ragged(const nvrx_segtailattr_args& a, hipStream_t st);
 // individual tail scores straight from those segments against the rows' history (segment_history.hip)
 hipError_t segment_history_scores_ragged(const nvrx_seghist_args& a, hipStream_t st);
+// the individual tail score attribution straight from those segments (segment_history_attribution.hip)
+hipError_t segment_history_attribution_ragged(const nvrx_seghistattr_args& a, hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

@@ -668,8 +668,8 @@ class MatrixReporter:
 
     def individual_tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor,
                                        permille: int = 990, threshold: Optional[float] = None,
-                                       absorb: str = "healthy",
-                                       tail_calls: bool = False) -> BatchIndividualTailScores:
+                                       absorb: str = "healthy", tail_calls: bool = False,
+                                       attribute: int = 0) -> BatchIndividualTailScores:
         """The individual tail scores of ``individual_tail_scores`` for the record streams
         ``report_records`` takes (recs [n, 2] int32 {slot, ns}, rec_off [R + 1] int64, device),
         over the windows that report retains (the last ``cap`` records of every rank and kernel)
@@ -684,9 +684,16 @@ class MatrixReporter:
         ``"healthy"`` -- a score launch, then an update launch that skips the flagged ranks on the
         device; ``"always"`` -- one fused launch; ``"never"`` -- score only.  It queues behind
         reports in flight and touches none of the report's buffers; the results come in one
-        device-to-host copy; ``.attribution`` is None (the individual attribution for record
-        streams is not built).  Beyond the reference."""
+        device-to-host copy.  ``attribute=top`` (1..16) adds ``.attribution`` as
+        ``individual_tail_scores(attribute=)`` does -- per rank the `top` kernels with the largest
+        excess tail time against the rank's own history, ``histograms.segment_history_attribution``
+        on the host -- again without the counts: ``ops.segment_history_attribution_ragged`` on the
+        call's own buckets, between the score and the update so that it sees the history the score
+        saw (``absorb="always"`` then runs a score-only launch, the attribution and an update-only
+        launch), packed behind the call's outputs in the same device-to-host copy.  Without it
+        ``.attribution`` stays None and the launches are what they were.  Beyond the reference."""
         pm = ops.tail_permille(permille)
+        top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
             raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
         if self.exchange:
@@ -700,6 +707,9 @@ class MatrixReporter:
         w = self._records_tail_work(n)
         t = self._history_tail_work()
         buf = t["buf"]
+        if top:  # the same layout at the head of a longer buffer
+            aoff = self._tail_attr_buffers(t, 41 * R)
+            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
         i64 = buf[:40 * R].view(torch.int64)
         out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
                                     i64[3 * R:4 * R], i64[4 * R:], buf[40 * R:41 * R])
@@ -709,14 +719,20 @@ class MatrixReporter:
         seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=w["bucket"])
         max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
         res = ops.segment_history_scores_ragged(
-            out_ns, seg_off, seg_len, K, max_len, t["hist"], permille=pm, update=absorb == "always",
-            aligned16=True, col_valid=self.col_valid,
+            out_ns, seg_off, seg_len, K, max_len, t["hist"], permille=pm,
+            update=absorb == "always" and not top, aligned16=True, col_valid=self.col_valid,
             score_thr=self.thr_ind if threshold is None else threshold,
             tail_calls=t["calls"] if tail_calls else False, out=out)
-        if absorb == "healthy":
+        if top:  # between the score and the update: the history the score saw
+            ops.segment_history_attribution_ragged(
+                out_ns, seg_off, seg_len, K, max_len, t["hist"], permille=pm, top=top,
+                aligned16=True, col_valid=self.col_valid,
+                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
+        if absorb == "healthy" or (absorb == "always" and top):
             ops.segment_history_scores_ragged(out_ns, seg_off, seg_len, K, max_len, t["hist"],
                                               permille=pm, score=False, aligned16=True,
-                                              col_valid=self.col_valid, skip_rows=out.strag)
+                                              col_valid=self.col_valid,
+                                              skip_rows=out.strag if absorb == "healthy" else None)
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
         h64 = host[:40 * R].view(np.uint64).reshape(5, R).copy()
         btail, btotal = h64[3], h64[4]
@@ -724,7 +740,9 @@ class MatrixReporter:
             share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
         return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
                                          host[40 * R:41 * R].astype(bool), btail, btotal,
-                                         res.tail_calls, None)
+                                         res.tail_calls,
+                                         BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
+                                         if top else None)
 
     def reset_tail_history(self) -> None:
         """Forget the history of ``individual_tail_scores``: the next interval scores NaN."""

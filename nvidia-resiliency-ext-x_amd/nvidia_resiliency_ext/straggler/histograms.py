@@ -485,6 +485,17 @@ def segment_tail_attribution(keys, seg_off, seg_len, K: int, permille: int, top:
                             thr_index=thr_index)
 
 
+def segment_history_attribution(keys, seg_off, seg_len, K: int, hist, permille: int, top: int,
+                                cap: int = 0, hist_index=None, col_valid=None) -> TailAttribution:
+    """The kernels behind the individual tail score of each row straight from ragged segments of
+    duration keys (``segment_counts``'s addressing) against the rows' own history ``hist`` (read
+    only), the host twin of ``ops.segment_history_attribution_ragged`` and of
+    ``MatrixReporter.individual_tail_scores_records(attribute=)``: ``history_attribution`` over
+    the retained windows' counts."""
+    return history_attribution(segment_counts(keys, seg_off, seg_len, K, cap), hist, permille, top,
+                               hist_index, col_valid)
+
+
 def quantile_bounds(counts, permille: int):
     """``(lo_us, hi_us)`` of the bucket that holds the quantile ``permille`` (an int in
     [0, 1000]) of the n samples counted in ``counts`` ([240]): the sample of 0-based rank
