@@ -33,7 +33,8 @@
  * nvrx_histogram_sum / _tail_threshold / _tail_scores, nvrx_histogram_history_scores,
  * nvrx_histogram_tail_base / _tail_attribution, nvrx_segment_fleet_histogram_ragged,
  * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged,
- * nvrx_segment_history_scores_ragged, nvrx_segment_history_attribution_ragged.
+ * nvrx_segment_history_scores_ragged, nvrx_segment_history_attribution_ragged,
+ * nvrx_segment_history_scores_compact_ragged.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -610,6 +611,84 @@ typedef struct nvrx_seghistattr_args {
     double* loss_all;           /* [R][K] */
 } nvrx_seghistattr_args;
 int nvrx_segment_history_attribution_ragged(const nvrx_seghistattr_args* args, void* stream);
+
+/* The individual tail scores of record streams against a COMPACT history: 64 bytes per (rank,
+ * kernel) in place of the dense 960.  No reference counterpart.  A real kernel's durations sit in
+ * one to three of the 240 buckets, so the compact history keeps at most NVRX_CHIST_ENTRIES used
+ * buckets per element and folds what does not fit into the nearest kept bucket below.
+ *
+ * Element layout (NVRX_CHIST_BYTES = 64 bytes, 16-byte aligned):
+ *   bytes  0..47  u32 count[12]
+ *   bytes 48..59  u8  bucket[12]
+ *   bytes 60..63  u32 n, the number of used entries
+ * Canonical form: n <= 12; entries 0..n-1 have strictly ascending bucket < 240 and count >= 1;
+ * entries n..11 are all zero.  An all-zero element is the empty history, so clearing the memory
+ * resets it.  The device assumes canonical input and always writes canonical output.
+ *
+ * The history is chist[R][stride] elements.  Segments, max_len, cap, aligned16, hist_index,
+ * hist_stride, col_valid, skip_rows, permille, mode and score_thr mean exactly what they do for
+ * nvrx_segment_history_scores_ragged.
+ *
+ * SCORE is exactly the score of nvrx_segment_history_scores_ragged with H set to the dense
+ * expansion of the element before the call: H[bucket[i]] = count[i] for i < n, zero elsewhere.
+ * Eligibility, T, the four u64 sums, tail_calls, the three separately rounded f64 operations and
+ * strag are unchanged.  The interval's sums come from the samples and are not affected by folding.
+ *
+ * UPDATE applies to every (r, k) that has col_valid[k], a slot s >= 0, skip_rows[r] = 0 and a
+ * retained length > 0.  With c[b] the counts of the retained window and S the element's used
+ * buckets:
+ *   admission    New = {b : c[b] > 0, b not in S} in ascending order; the first
+ *                min(|New|, 12 - |S|) of them are admitted, giving S'.
+ *   target       for every b with c[b] > 0: t(b) = max{s in S' : s <= b}, or min S' if there is
+ *                no such s.
+ *   new counts   count'[t] = min(count[t] + sum_{b : t(b) = t} c[b], 2^32 - 1), the sum taken in 64
+ *                bits, so the order of the adds cannot matter.
+ *   result       the entries re-sorted, n = |S'|: canonical.
+ *   folded[r]    (u64) the sum of c[b] over b not in S' over the row's updated elements; cleared
+ *                on the stream first; written only when the UPDATE bit is set.
+ * S' is never empty when there is a sample.  An element without samples is bit-identical
+ * afterwards and its 64 bytes are not written.  SCORE | UPDATE scores against the history from
+ * before the update.
+ *
+ * Relation to the dense history: where no element ever exceeds 12 buckets (folded == 0) the
+ * compact history expands to exactly the dense history nvrx_segment_history_scores_ragged
+ * produces, and every output is bit-identical to that entry's.  Folding conserves N (away from
+ * saturation), so the rank rule stays meaningful; it only moves weight to a lower edge, and folded
+ * says how much.
+ *
+ * chist 16-byte aligned; seg_off, the four u64 outputs, score and folded 8-byte aligned; mode needs
+ * at least one bit; permille in 0..1000; the retained run at most NVRX_MAX_SEGMENT; K * 240 and
+ * R * K below 2^31.  folded is required with UPDATE and must not alias the other outputs.  Two
+ * columns must not share a slot.  R == 0 or K == 0 launches nothing.  Stream-ordered: kernels on
+ * `stream` only, no allocation, no synchronisation, no host read-back, no scratch; capturable as
+ * a linear chain. */
+#define NVRX_CHIST_ENTRIES 12
+#define NVRX_CHIST_BYTES 64
+typedef struct nvrx_segchist_args {
+    int64_t R, K;
+    const uint32_t* ns;         /* duration keys */
+    const int64_t* seg_off;     /* [R * K] (+ 1 without seg_len) */
+    const int32_t* seg_len;     /* [R * K] or NULL */
+    int64_t max_len, cap;
+    int32_t aligned16;          /* the caller's word that every retained run starts 16-byte aligned */
+    void* chist;                /* [R][hist_stride] elements of NVRX_CHIST_BYTES, in place */
+    int64_t hist_stride;        /* in elements; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* [K] or NULL */
+    const uint8_t* skip_rows;   /* [R] or NULL */
+    int32_t permille;
+    int32_t mode;               /* NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE */
+    double score_thr;
+    uint64_t* tail_ns;          /* [R] */
+    uint64_t* total_ns;         /* [R] */
+    uint64_t* base_tail_ns;     /* [R] */
+    uint64_t* base_total_ns;    /* [R] */
+    double* score;              /* [R] */
+    uint8_t* strag;             /* [R] or NULL */
+    uint32_t* tail_calls;       /* [R][K] or NULL */
+    uint64_t* folded;           /* [R]; required with UPDATE */
+} nvrx_segchist_args;
+int nvrx_segment_history_scores_compact_ragged(const nvrx_segchist_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

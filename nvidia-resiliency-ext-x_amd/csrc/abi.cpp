@@ -494,6 +494,57 @@ int nvrx_segment_history_scores_ragged(const nvrx_seghist_args* a, void* stream)
     return hip_status(nvrx::segment_history_scores_ragged(b, S(stream)), fn.c_str());
 }
 
+// the same scores against a compact history of 64 B per element (segment_history_compact.hip)
+int nvrx_segment_history_scores_compact_ragged(const nvrx_segchist_args* a, void* stream) {
+    const std::string fn("nvrx_segment_history_scores_compact_ragged");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
+                              a->max_len, a->cap))
+        return rc;
+    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
+                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
+    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                   fn + ": hist_stride below K without hist_index");
+    const bool score = a->mode & NVRX_HTAIL_SCORE, update = a->mode & NVRX_HTAIL_UPDATE;
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->chist, fn + ": null chist");
+        if (score) {
+            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
+            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
+            NVRX_CHECK_ARG(a->score, fn + ": null score");
+        }
+        if (update) {
+            NVRX_CHECK_ARG(a->folded, fn + ": null folded");
+            if (score) {
+                const void* const outs[] = {a->tail_ns, a->total_ns, a->base_tail_ns,
+                                            a->base_total_ns, a->score};
+                for (const void* o : outs)
+                    NVRX_CHECK_ARG(o != (const void*)a->folded, fn + ": folded aliases another output");
+            }
+        }
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->chist & 15) == 0, fn + ": chist not 16-byte aligned");
+    if (score) {
+        NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->base_tail_ns & 7) == 0, fn + ": base_tail_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->base_total_ns & 7) == 0,
+                       fn + ": base_total_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
+    }
+    if (update) NVRX_CHECK_ARG(((uintptr_t)a->folded & 7) == 0, fn + ": folded not 8-byte aligned");
+    nvrx_segchist_args b = *a;
+    if (!score) b.tail_calls = nullptr;  // ignored without SCORE
+    if (!update) b.folded = nullptr;     // not written without UPDATE
+    return hip_status(nvrx::segment_history_scores_compact_ragged(b, S(stream)), fn.c_str());
+}
+
 // the individual tail score attribution straight from those segments
 // (segment_history_attribution.hip)
 int nvrx_segment_history_attribution_ragged(const nvrx_seghistattr_args* a, void* stream) {

@@ -64,6 +64,9 @@ hipError_t segment_tail_attribution_ragged(const nvrx_segtailattr_args& a, hipSt
 hipError_t segment_history_scores_ragged(const nvrx_seghist_args& a, hipStream_t st);
 // the individual tail score attribution straight from those segments (segment_history_attribution.hip)
 hipError_t segment_history_attribution_ragged(const nvrx_seghistattr_args& a, hipStream_t st);
+// individual tail scores straight from those segments against a compact history
+// (segment_history_compact.hip)
+hipError_t segment_history_scores_compact_ragged(const nvrx_segchist_args& a, hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

@@ -1,0 +1,365 @@
+// segment_history_compact.hip -- individual tail scores straight from ragged segments against a
+// compact history, on gfx950.
+//
+// No reference counterpart.  segment_history.hip scores a rank against a dense history of 240 u32
+// bins per (rank, kernel): 960 B, of which a real kernel uses one to three bins.  Here an element
+// is 64 B (include/nvrx_straggler.h, "compact history"): u32 count[12], u8 bucket[12], u32 n, the
+// used entries in ascending bucket order.  SCORE is segment_history.hip's score with H the dense
+// expansion of the element; UPDATE admits the interval's new buckets in ascending order while
+// entries are free and folds every other sample into the nearest kept bucket at or below it (the
+// lowest kept one if there is none), counting the folded samples per row.
+//
+//   segchist_kernel    the grid (rows, splits of K), the split rule and the 16-element workgroup
+//                      trip of seghist_kernel.  A wave takes SC_UNROLL = 4 (row, kernel) elements
+//                      per trip and loads them with ONE instruction: DPP row u (lanes 16u..16u+15)
+//                      holds element u, one dword per lane -- lanes 0..11 a count, 12..14 the
+//                      bucket bytes, 15 n.  A bpermute inside the row hands each count lane its
+//                      bucket byte; the u64 row_shr prefix over the counts gives N in the row's
+//                      last lane, a ballot over the row the entry that holds the sample of rank
+//                      (pm (N - 1)) / 1000, a readlane its bucket T.  The base sums are
+//                      count * weight_of(bucket) per lane.  The retained run is walked as in
+//                      segment_history.hip: 64 samples per load, SC_LOADS loads in flight, per-lane
+//                      u64 total / tail, the calls by ballot and population count.
+//                      With UPDATE the interval's bins are counted in a wave-private LDS histogram
+//                      of 256 words (count_wave of segment_history.hip), chosen over carrying
+//                      count_wave's leaders in registers because the merge needs every bin in
+//                      bucket order and the 16 words behind the 240 bins hold the element being
+//                      built.  The merge: a lane owns four bins; the used buckets mark their lanes
+//                      (a loop over n <= 12 entries, readlanes); the new buckets are ranked by a
+//                      wave prefix over the population counts and admitted while entries are free;
+//                      a second prefix over the kept buckets gives every bin the index of its
+//                      target entry, to which its count is added in LDS (u32: a run is at most
+//                      2^30 samples); the lane that owns a kept bucket then adds the old count,
+//                      saturating, and writes count and bucket byte at the entry's index.  16 lanes
+//                      store the 64 B.  Each (row, slot) has one owner: no atomics on the history.
+//                      Row sums and folded: DPP + LDS reduction, the non-zero sums added with
+//                      64-bit device atomics (cleared by a kernel on the stream first).  Integer
+//                      adds are exact in any order: the result is the same on every run.
+//   segchist_finalize  the three separately rounded f64 operations and strag, as seghist_finalize.
+// bucket_of, sat_add, count_wave, the clear and the finalize restate what segment_history.hip
+// holds in its anonymous namespace; no existing file changes.  Every loop is bounded by K, by the
+// retained length or by 12.  No kernel uses scratch memory (make asm).
+
+#include "histogram_wave.h"
+#include "segment_addr.h"
+
+namespace nvrx {
+namespace {
+
+constexpr int SC_THREADS = 256;
+constexpr int SC_WAVES = SC_THREADS / 64;
+constexpr int SC_UNROLL = 4;                     // elements per wave trip: one per DPP row
+constexpr int SC_TRIP = SC_WAVES * SC_UNROLL;    // elements per workgroup trip: a split's granule
+constexpr int SC_TARGET_WGS = 2048;              // 256 CUs x 8 workgroups
+constexpr int SC_LOADS = 4;                      // sample loads in flight per lane
+constexpr int SC_HW = 256;                       // LDS words per wave: 240 bins + the element built
+constexpr int SC_E = NVRX_CHIST_ENTRIES;
+constexpr int SC_WORDS = NVRX_CHIST_BYTES / 4;   // 16: one DPP row
+constexpr unsigned SC_NONE = HB;                 // the bucket of a lane past the run's end
+static_assert(SC_WORDS == 16 && SC_UNROLL * SC_WORDS == NVRX_WAVE, "an element is one DPP row");
+static_assert(SC_HW == HB + SC_WORDS && SC_HW == 4 * NVRX_WAVE, "one 16-byte vector per lane clears it");
+static_assert(4 * SC_E + SC_E + 4 == NVRX_CHIST_BYTES, "count[12], bucket[12], n");
+
+// segment_histogram.hip's bucket expression: sh = e - 3 for x >= 8, 0 below
+__device__ __forceinline__ unsigned bucket_of(unsigned x) {
+    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
+    return (sh << 3) + (x >> sh);
+}
+
+__device__ __forceinline__ unsigned sat_add(unsigned h, unsigned c) {
+    const unsigned s = h + c;
+    return s < h ? 0xFFFFFFFFu : s;  // min(h + c, 2^32 - 1) of the 64-bit sum
+}
+
+// 64 buckets, one per lane (SC_NONE: no sample), into the wave's bins h
+__device__ __forceinline__ void count_wave(unsigned b, unsigned* h) {
+    uint64_t live = __ballot(b != SC_NONE);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        if (!live) return;  // wave-uniform
+        const int l = __builtin_ctzll(live);
+        const unsigned lead = rl(b, l);
+        const uint64_t same = __ballot(b == lead);
+        if (lane_id() == l) atomicAdd(&h[lead], (unsigned)__popcll(same));
+        live &= ~same;
+    }
+    if ((live >> lane_id()) & 1) atomicAdd(&h[b], 1u);
+}
+
+// the wave's LDS operations before this are done and visible before those after it
+__device__ __forceinline__ void lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// inclusive u64 prefix inside each 16-lane row (row_shr zero-fills at the row's start)
+__device__ __forceinline__ u64 row_incl_scan_u64(u64 v) {
+    v += dpp_u64<0x111>(v);
+    v += dpp_u64<0x112>(v);
+    v += dpp_u64<0x114>(v);
+    v += dpp_u64<0x118>(v);
+    return v;
+}
+
+__global__ __launch_bounds__(256)
+void segchist_clear_kernel(u64* a, u64* b, u64* c, u64* d, u64* folded, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (a) {  // SCORE
+        a[i] = 0ull;
+        b[i] = 0ull;
+        c[i] = 0ull;
+        d[i] = 0ull;
+    }
+    if (folded) folded[i] = 0ull;  // UPDATE
+}
+
+// kernels [blockIdx.y * kper, + kper) of row blockIdx.x
+template <bool SCORE, bool UPDATE, bool CALLS>
+__global__ __launch_bounds__(SC_THREADS)
+void segchist_kernel(RaggedSegs segs, nvrx_segchist_args a, int64_t kper) {
+    static_assert(SCORE || UPDATE, "nothing to do");
+    static_assert(SCORE || !CALLS, "tail_calls belong to the score");
+    __shared__ u64 red[SC_WAVES][4];
+    __shared__ __attribute__((aligned(16))) unsigned bins[UPDATE ? SC_WAVES * SC_HW : 4];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = lane_id();
+    const int row = lane >> 4, j = lane & 15;  // the element of the trip this lane holds a word of
+    const int64_t r = blockIdx.x;
+    const int64_t K = a.K;
+    const bool absorb = UPDATE && !(a.skip_rows && a.skip_rows[r]);  // workgroup-uniform
+    const int64_t kb = (int64_t)blockIdx.y * kper;
+    // a skipped row of the update-only pass has no work
+    const int64_t ke = SCORE || absorb ? min(K, kb + kper) : kb;
+    const int64_t stride = a.hist_stride ? a.hist_stride : K;
+    unsigned* const crow = (unsigned*)a.chist + r * stride * SC_WORDS;
+    const int pm = a.permille;
+    unsigned* const hb = bins + (UPDATE ? wave * SC_HW : 0);
+    u64 total = 0, tail = 0, btotal = 0, btail = 0, fold = 0;
+    for (int64_t k0 = kb + wave; k0 < ke; k0 += SC_TRIP) {
+        int64_t slot[SC_UNROLL];
+        const uint32_t* run[SC_UNROLL];
+        int len[SC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SC_UNROLL; ++u) {
+            const int64_t k = k0 + u * SC_WAVES;  // wave-uniform, and so is all that follows from it
+            slot[u] = -1;
+            run[u] = nullptr;
+            len[u] = 0;
+            if (k < ke) {
+                int64_t s = a.hist_index ? (int64_t)a.hist_index[k] : k;
+                if (a.col_valid && !a.col_valid[k]) s = -1;
+                if (s >= 0) segs.get(r * K + k, run[u], len[u]);
+                if (len[u] <= 0) s = -1;  // an empty element: no score, no update, no read of the history
+                slot[u] = s;
+            }
+        }
+        // the trip's four elements in one load: row u, word j
+        const int64_t sl = row == 0 ? slot[0] : row == 1 ? slot[1] : row == 2 ? slot[2] : slot[3];
+        const unsigned word = sl >= 0 ? crow[sl * SC_WORDS + j] : 0u;
+        // lanes 0..11 of a row: the entry's count and bucket (zero beyond n, by the canonical form)
+        const unsigned bytes = (unsigned)__builtin_amdgcn_ds_bpermute(4 * ((lane & 48) + SC_E + (j >> 2)),
+                                                                      (int)word);
+        const bool entry = j < SC_E;
+        const unsigned cnt = entry ? word : 0u;
+        const unsigned bkt = entry ? (bytes >> (8 * (j & 3))) & 0xFFu : 0u;
+        const u64 incl = SCORE ? row_incl_scan_u64((u64)cnt) : 0ull;
+        const u64 wsum = (u64)cnt * weight_of((int)bkt);
+#pragma unroll
+        for (int u = 0; u < SC_UNROLL; ++u) {
+            const int64_t k = k0 + u * SC_WAVES;
+            const int64_t s = slot[u];
+            if (s < 0) {  // wave-uniform
+                if (CALLS && k < ke && lane == 0) a.tail_calls[r * K + k] = 0u;
+                continue;
+            }
+            const uint32_t* const q = run[u];
+            const int m = len[u];
+            const bool mine = row == u;
+            const bool count = UPDATE && absorb;
+            bool elig = false;
+            int t = HB;  // no bucket lies above it
+            if (SCORE) {
+                const u64 N = rl_u64(incl, 16 * u + 15);  // lanes 12..15 add nothing
+                if (N != 0) {
+                    elig = true;
+                    // (pm (N - 1)) / 1000 without the product leaving 64 bits
+                    const u64 d = (N - 1) / 1000ull, mm = (N - 1) % 1000ull;
+                    const u64 rank = (u64)pm * d + ((u64)pm * mm) / 1000ull;
+                    // incl is non-decreasing over the row and incl[11] = N > rank: the entries at
+                    // or below rank are a prefix, and the entry after them has a count
+                    const int L = (int)__popcll(__ballot(mine && incl <= rank));
+                    t = (int)rl(bkt, 16 * u + L);
+                    if (mine) {
+                        btotal += wsum;
+                        btail += (int)bkt > t ? wsum : 0ull;
+                    }
+                }
+            }
+            if (count) {
+                *(u32x4*)(hb + 4 * lane) = (u32x4){0u, 0u, 0u, 0u};
+                lds_order();
+            }
+            unsigned calls = 0;
+            if (elig || count) {  // wave-uniform
+                for (int base = 0; base < m; base += 64 * SC_LOADS) {
+                    unsigned x[SC_LOADS];
+#pragma unroll
+                    for (int v = 0; v < SC_LOADS; ++v) {
+                        const int i = base + v * 64 + lane;
+                        x[v] = i < m ? __builtin_nontemporal_load(q + i) : 0u;
+                    }
+#pragma unroll
+                    for (int v = 0; v < SC_LOADS; ++v) {
+                        if (base + v * 64 >= m) break;  // wave-uniform
+                        const bool live = base + v * 64 + lane < m;
+                        const unsigned b = bucket_of(x[v]);
+                        if (SCORE && elig) {
+                            const u64 w = live ? (u64)weight_of((int)b) : 0ull;
+                            const bool hit = live && (int)b > t;
+                            total += w;
+                            tail += hit ? w : 0ull;
+                            if (CALLS) calls += (unsigned)__popcll(__ballot(hit));
+                        }
+                        if (count) count_wave(live ? b : SC_NONE, hb);
+                    }
+                }
+            }
+            if (CALLS && lane == 0) a.tail_calls[r * K + k] = calls;
+            if (count) {
+                lds_order();
+                // this lane's four bins (lanes 60..63 read the zeroed words behind the bins)
+                const u32x4 c = *(const u32x4*)(hb + 4 * lane);
+                const int n = (int)rl(word, 16 * u + 15);  // <= 12 by the canonical form
+                unsigned used = 0, o0 = 0, o1 = 0, o2 = 0, o3 = 0;  // S and its counts, by bin
+                for (int e = 0; e < min(n, SC_E); ++e) {
+                    const unsigned eb = rl(bkt, 16 * u + e), ec = rl(cnt, 16 * u + e);
+                    if (lane == (int)(eb >> 2)) {
+                        const unsigned w = eb & 3u;
+                        used |= 1u << w;
+                        o0 = w == 0 ? ec : o0;
+                        o1 = w == 1 ? ec : o1;
+                        o2 = w == 2 ? ec : o2;
+                        o3 = w == 3 ? ec : o3;
+                    }
+                }
+                const unsigned have = (c.x ? 1u : 0u) | (c.y ? 2u : 0u) | (c.z ? 4u : 0u) | (c.w ? 8u : 0u);
+                // admission: the new buckets in ascending order while entries are free
+                const unsigned fresh = have & ~used;
+                const unsigned nf = (unsigned)__builtin_popcount(fresh);
+                const unsigned before = wave_incl_scan_u32(nf) - nf;
+                const unsigned room = (unsigned)(SC_E - min(n, SC_E));
+                unsigned kept = used;
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+                    if (((fresh >> w) & 1u) && before + (unsigned)__builtin_popcount(fresh & ((1u << w) - 1u)) < room)
+                        kept |= 1u << w;
+                // the entry index of every kept bucket, and through it every bin's target
+                const unsigned nk = (unsigned)__builtin_popcount(kept);
+                const unsigned below = wave_incl_scan_u32(nk) - nk;
+                const unsigned n2 = rl(below + nk, 63);  // |S'| >= 1: the run has a sample
+                const unsigned cc[4] = {c.x, c.y, c.z, c.w};
+                const unsigned oo[4] = {o0, o1, o2, o3};
+                unsigned at[4];
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    // kept buckets at or below bin 4 lane + w; none: the lowest kept one
+                    const unsigned upto = below + (unsigned)__builtin_popcount(kept & ((2u << w) - 1u));
+                    at[w] = max(upto, 1u) - 1u;
+                    if (cc[w]) {
+                        atomicAdd(&hb[HB + at[w]], cc[w]);
+                        if (!((kept >> w) & 1u)) fold += cc[w];
+                    }
+                }
+                lds_order();
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    if ((kept >> w) & 1u) {  // the one owner of entry at[w]
+                        hb[HB + at[w]] = sat_add(oo[w], hb[HB + at[w]]);
+                        ((unsigned char*)(hb + HB + SC_E))[at[w]] = (unsigned char)(4 * lane + w);
+                    }
+                }
+                if (lane == 0) hb[HB + SC_WORDS - 1] = n2;
+                lds_order();
+                if (lane < SC_WORDS) crow[s * SC_WORDS + lane] = hb[HB + lane];
+            }
+        }
+    }
+    if (UPDATE) {
+        fold = wave_sum_u64(fold);
+        if (lane == 0 && fold) atomicAdd((u64*)a.folded + r, fold);
+    }
+    if (!SCORE) return;  // the update-only instantiation has no barrier
+    total = wave_sum_u64(total);
+    tail = wave_sum_u64(tail);
+    btotal = wave_sum_u64(btotal);
+    btail = wave_sum_u64(btail);
+    if (lane == 0) {
+        red[wave][0] = tail;
+        red[wave][1] = total;
+        red[wave][2] = btail;
+        red[wave][3] = btotal;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 4) return;
+    u64 v = 0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) v += red[w][threadIdx.x];
+    uint64_t* const dst = threadIdx.x == 0 ? a.tail_ns : threadIdx.x == 1 ? a.total_ns
+                        : threadIdx.x == 2 ? a.base_tail_ns : a.base_total_ns;
+    if (v) atomicAdd((u64*)dst + r, v);
+}
+
+__global__ __launch_bounds__(256) void segchist_finalize_kernel(nvrx_segchist_args a) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const u64 tl = a.tail_ns[r], tt = a.total_ns[r], bl = a.base_tail_ns[r], bt = a.base_total_ns[r];
+    double score = __builtin_nan("");
+    if (tt != 0 && bt != 0) {
+        const double share = (double)tl / (double)tt;
+        const double bs = (double)bl / (double)bt;
+        const double den = 1.0 - bs;
+        if (den != 0.0) score = (1.0 - share) / den;
+    }
+    a.score[r] = score;
+    if (a.strag) a.strag[r] = score < a.score_thr;  // NaN compares false
+}
+
+template <bool SCORE, bool UPDATE, bool CALLS>
+void launch_segchist(const nvrx_segchist_args& a, dim3 grid, int64_t kper, hipStream_t st) {
+    hipLaunchKernelGGL((segchist_kernel<SCORE, UPDATE, CALLS>), grid, dim3(SC_THREADS), 0, st,
+                       RaggedSegs{a.ns, a.seg_off, a.seg_len, a.cap}, a, kper);
+}
+
+}  // namespace
+
+// Argument checks happen in abi.cpp before this runs.
+hipError_t segment_history_scores_compact_ragged(const nvrx_segchist_args& a, hipStream_t st) {
+    if (a.R <= 0 || a.K <= 0) return hipSuccess;
+    const bool score = a.mode & NVRX_HTAIL_SCORE, update = a.mode & NVRX_HTAIL_UPDATE;
+    // the split rule of segment_history.hip: about SC_TARGET_WGS workgroups over rows x splits, a
+    // split no shorter than one workgroup trip (SC_TRIP kernels) and a whole number of trips
+    int64_t splits = (SC_TARGET_WGS + a.R - 1) / a.R;
+    splits = min(splits, (a.K + SC_TRIP - 1) / SC_TRIP);
+    int64_t kper = (a.K + splits - 1) / splits;
+    kper = (kper + SC_TRIP - 1) / SC_TRIP * SC_TRIP;
+    splits = (a.K + kper - 1) / kper;  // <= SC_TARGET_WGS: fits grid.y
+    const dim3 grid((unsigned)a.R, (unsigned)splits);
+    const dim3 rows((unsigned)((a.R + 255) / 256));
+    hipLaunchKernelGGL(segchist_clear_kernel, rows, dim3(256), 0, st,
+                       score ? (u64*)a.tail_ns : nullptr, (u64*)a.total_ns, (u64*)a.base_tail_ns,
+                       (u64*)a.base_total_ns, update ? (u64*)a.folded : nullptr, a.R);
+    if (!score)
+        launch_segchist<false, true, false>(a, grid, kper, st);
+    else if (update)
+        a.tail_calls ? launch_segchist<true, true, true>(a, grid, kper, st)
+                     : launch_segchist<true, true, false>(a, grid, kper, st);
+    else
+        a.tail_calls ? launch_segchist<true, false, true>(a, grid, kper, st)
+                     : launch_segchist<true, false, false>(a, grid, kper, st);
+    if (score) hipLaunchKernelGGL(segchist_finalize_kernel, rows, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace nvrx

@@ -108,6 +108,20 @@ class SegHistArgs(ctypes.Structure):
     ]
 
 
+CHIST_ENTRIES = 12  # NVRX_CHIST_ENTRIES: used buckets a compact history element keeps
+CHIST_BYTES = 64    # NVRX_CHIST_BYTES: u32 count[12], u8 bucket[12], u32 n
+
+
+class SegCHistArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("ns", P), ("seg_off", P), ("seg_len", P), ("max_len", i64),
+        ("cap", i64), ("aligned16", i32), ("chist", P), ("hist_stride", i64), ("hist_index", P),
+        ("col_valid", P), ("skip_rows", P), ("permille", i32), ("mode", i32), ("score_thr", f64),
+        ("tail_ns", P), ("total_ns", P), ("base_tail_ns", P), ("base_total_ns", P), ("score", P),
+        ("strag", P), ("tail_calls", P), ("folded", P),
+    ]
+
+
 class TailAttrArgs(ctypes.Structure):
     _fields_ = [
         ("R", i64), ("K", i64), ("counts", P), ("kind", i32), ("top", i32), ("thr", P),
@@ -188,6 +202,7 @@ SIGNATURES = {
     "nvrx_segment_tail_attribution_ragged": (ctypes.c_int, [ctypes.POINTER(SegTailAttrArgs), P]),
     "nvrx_segment_history_scores_ragged": (ctypes.c_int, [ctypes.POINTER(SegHistArgs), P]),
     "nvrx_segment_history_attribution_ragged": (ctypes.c_int, [ctypes.POINTER(SegHistAttrArgs), P]),
+    "nvrx_segment_history_scores_compact_ragged": (ctypes.c_int, [ctypes.POINTER(SegCHistArgs), P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

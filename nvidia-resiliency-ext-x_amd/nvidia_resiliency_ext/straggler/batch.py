@@ -111,6 +111,7 @@ class BatchIndividualTailScores:
     base_tail_ns: np.ndarray      # [R] u64
     base_total_ns: np.ndarray     # [R] u64
     tail_calls: Optional[torch.Tensor] = None  # [R, K] int32 on the device, on request
+    folded: Optional[np.ndarray] = None  # [R] u64 samples folded, with history="compact"
     attribution: Optional[BatchTailAttribution] = None  # with attribute > 0
 
 
@@ -225,6 +226,7 @@ class MatrixReporter:
         self._tail = None  # tail_scores(): fleet histogram and packed outputs, allocated at first use
         self._htail = None  # individual_tail_scores(): [R][K][240] history and packed outputs, likewise
         self._rtail = None  # tail_scores_records(): bucketing work tensors, fleet histogram, packed outputs
+        self._ctail = None  # individual_tail_scores_records(history="compact"): [R][K][64] history, packed outputs
 
     @property
     def stats(self) -> ops.SegmentStats:
@@ -663,13 +665,14 @@ class MatrixReporter:
         return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
                                          host[40 * R:41 * R].astype(bool), btail, btotal,
                                          res.tail_calls,
-                                         BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
-                                         if top else None)
+                                         attribution=BatchTailAttribution.unpack(
+                                             host[aoff:], R, top, t["loss_all"]) if top else None)
 
     def individual_tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor,
                                        permille: int = 990, threshold: Optional[float] = None,
                                        absorb: str = "healthy", tail_calls: bool = False,
-                                       attribute: int = 0) -> BatchIndividualTailScores:
+                                       attribute: int = 0,
+                                       history: str = "dense") -> BatchIndividualTailScores:
         """The individual tail scores of ``individual_tail_scores`` for the record streams
         ``report_records`` takes (recs [n, 2] int32 {slot, ns}, rec_off [R + 1] int64, device),
         over the windows that report retains (the last ``cap`` records of every rank and kernel)
@@ -691,20 +694,38 @@ class MatrixReporter:
         call's own buckets, between the score and the update so that it sees the history the score
         saw (``absorb="always"`` then runs a score-only launch, the attribution and an update-only
         launch), packed behind the call's outputs in the same device-to-host copy.  Without it
-        ``.attribution`` stays None and the launches are what they were.  Beyond the reference."""
+        ``.attribution`` stays None and the launches are what they were.
+        ``history="compact"`` scores against, and folds the interval into, a SEPARATE compact
+        history of 64 bytes per (rank, kernel) in place of 960 (uint8 [R, K, 64], allocated at
+        first use; ``compact_tail_history()`` returns it, ``reset_tail_history`` clears both):
+        ``ops.segment_history_scores_compact_ragged`` with the same ``absorb`` logic.  An element
+        keeps at most 12 used buckets and folds what does not fit into the nearest kept bucket
+        below; ``.folded`` (u64 [R], in the same device-to-host copy) counts the samples folded in
+        this call, and while it stays 0 every result equals ``history="dense"``'s bit for bit
+        (``histograms.segment_compact_history_scores`` on the host).  ``attribute`` is not
+        available against the compact history yet (NotImplementedError).  ``history="dense"``
+        (default) is the path described above, untouched.  Beyond the reference."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
             raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
+        if history not in ("dense", "compact"):
+            raise ValueError(f"history must be 'dense' or 'compact', got {history!r}")
         if self.exchange:
             raise NotImplementedError("MatrixReporter.individual_tail_scores_records: tail scores "
                                       "across kernel shards (exchange=True) are not supported")
+        if history == "compact" and top:
+            raise NotImplementedError("MatrixReporter.individual_tail_scores_records: attribution "
+                                      "against the compact history is not supported")
         R, K, d = self.R, self.K, self.device
         if rec_off.numel() != R + 1:
             raise ValueError(f"rec_off must hold {R + 1} offsets")
         self._order_after_inflight()
         n = recs.shape[0]
         w = self._records_tail_work(n)
+        if history == "compact":
+            return self._individual_tail_scores_records_compact(recs, rec_off, w, pm, threshold,
+                                                                absorb, tail_calls)
         t = self._history_tail_work()
         buf = t["buf"]
         if top:  # the same layout at the head of a longer buffer
@@ -741,14 +762,66 @@ class MatrixReporter:
         return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
                                          host[40 * R:41 * R].astype(bool), btail, btotal,
                                          res.tail_calls,
-                                         BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
-                                         if top else None)
+                                         attribution=BatchTailAttribution.unpack(
+                                             host[aoff:], R, top, t["loss_all"]) if top else None)
+
+    def _individual_tail_scores_records_compact(self, recs, rec_off, w, pm, threshold, absorb,
+                                                tail_calls) -> BatchIndividualTailScores:
+        """``individual_tail_scores_records(history="compact")`` after its checks: the launches of
+        the dense path with ``ops.segment_history_scores_compact_ragged`` on the compact history."""
+        R, K, d = self.R, self.K, self.device
+        if self._ctail is None:
+            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns][folded i64 R][strag u8 R]
+            self._ctail = dict(buf=torch.zeros(49 * R, dtype=torch.uint8, device=d),
+                               chist=torch.zeros((R, K, histograms.CHIST_BYTES), dtype=torch.uint8,
+                                                 device=d),
+                               calls=None)
+        t = self._ctail
+        buf = t["buf"]
+        i64 = buf[:48 * R].view(torch.int64)
+        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
+                                    i64[3 * R:4 * R], i64[4 * R:5 * R], buf[48 * R:])
+        folded = i64[5 * R:]
+        if tail_calls and t["calls"] is None:
+            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
+        n = recs.shape[0]
+        seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=w["bucket"])
+        max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
+        res, _ = ops.segment_history_scores_compact_ragged(
+            out_ns, seg_off, seg_len, K, max_len, t["chist"], permille=pm,
+            update=absorb == "always", aligned16=True, col_valid=self.col_valid,
+            score_thr=self.thr_ind if threshold is None else threshold,
+            tail_calls=t["calls"] if tail_calls else False, out=out, folded=folded)
+        if absorb == "healthy":
+            ops.segment_history_scores_compact_ragged(
+                out_ns, seg_off, seg_len, K, max_len, t["chist"], permille=pm, score=False,
+                aligned16=True, col_valid=self.col_valid, skip_rows=out.strag, folded=folded)
+        elif absorb == "never":
+            folded.zero_()  # no update: nothing folded
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        h64 = host[:48 * R].view(np.uint64).reshape(6, R).copy()
+        btail, btotal = h64[3], h64[4]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
+        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
+                                         host[48 * R:].astype(bool), btail, btotal,
+                                         res.tail_calls, folded=h64[5])
+
+    def compact_tail_history(self) -> Optional[torch.Tensor]:
+        """The compact history of ``individual_tail_scores_records(history="compact")`` (uint8
+        [R, K, 64] on the device; ``histograms.compact_to_dense`` expands a host copy), or None
+        before its first use."""
+        return None if self._ctail is None else self._ctail["chist"]
 
     def reset_tail_history(self) -> None:
-        """Forget the history of ``individual_tail_scores``: the next interval scores NaN."""
-        if self._htail is not None:
+        """Forget the histories of ``individual_tail_scores`` (dense and compact): the next
+        interval scores NaN."""
+        if self._htail is not None or self._ctail is not None:
             self._order_after_inflight()
+        if self._htail is not None:
             self._htail["hist"].zero_()
+        if self._ctail is not None:
+            self._ctail["chist"].zero_()
 
     def attribute(self, top: int = 8, kind: str = "relative") -> BatchAttribution:
         """Which kernels made each rank's score what it is: per rank the `top` (1..16) kernels

@@ -30,6 +30,11 @@ from ragged segments, without the counts (``ops.segment_fleet_histogram_ragged``
 ``ops.segment_tail_scores_ragged``, ``MatrixReporter.tail_scores_records``), and
 ``segment_tail_attribution`` of their attribution (``ops.segment_tail_attribution_ragged``,
 ``MatrixReporter.tail_scores_records(attribute=)``).
+``compact_to_dense`` / ``compact_from_dense`` / ``compact_is_canonical`` /
+``compact_history_scores`` / ``segment_compact_history_scores`` are the host side of the compact
+history (64 bytes per rank and kernel: at most 12 used buckets, further ones folded downwards;
+``ops.segment_history_scores_compact_ragged``,
+``MatrixReporter.individual_tail_scores_records(history="compact")``).
 """
 from __future__ import annotations
 
@@ -323,6 +328,172 @@ def segment_history_scores(keys, seg_off, seg_len, K: int, hist, permille: int, 
     ``ops.segment_history_scores_ragged`` and of ``MatrixReporter.individual_tail_scores_records``:
     ``history_scores`` (its keywords pass through) over the retained windows' counts."""
     return history_scores(segment_counts(keys, seg_off, seg_len, K, cap), hist, permille, **kwargs)
+
+
+CHIST_ENTRIES = 12  # NVRX_CHIST_ENTRIES
+CHIST_BYTES = 64    # NVRX_CHIST_BYTES: u32 count[12], u8 bucket[12], u32 n
+
+
+def _chist_array(chist) -> np.ndarray:
+    c = np.asarray(chist)
+    if c.dtype != np.uint8 or c.ndim != 3 or c.shape[2] != CHIST_BYTES:
+        raise ValueError(f"chist must be a uint8 array of shape [R, S, {CHIST_BYTES}]")
+    return np.ascontiguousarray(c)
+
+
+def _chist_fields(c: np.ndarray):
+    """(count [.., 12] int64, bucket [.., 12] int64, n [..] int64) of compact elements."""
+    count = c[..., :4 * CHIST_ENTRIES].view("<u4").astype(np.int64)
+    bucket = c[..., 4 * CHIST_ENTRIES:5 * CHIST_ENTRIES].astype(np.int64)
+    n = c[..., 5 * CHIST_ENTRIES:].view("<u4")[..., 0].astype(np.int64)
+    return count, bucket, n
+
+
+def compact_is_canonical(chist) -> np.ndarray:
+    """Per element of a compact history (uint8 [R, S, 64]) whether it is canonical: n <= 12,
+    entries 0..n-1 with strictly ascending bucket < 240 and count >= 1, entries n..11 all zero
+    (bool [R, S]; the all-zero element is the empty history)."""
+    count, bucket, n = _chist_fields(_chist_array(chist))
+    i = np.arange(CHIST_ENTRIES)
+    used = i < n[..., None]
+    ok = n <= CHIST_ENTRIES
+    ok &= np.where(used, (count >= 1) & (bucket < BINS), (count == 0) & (bucket == 0)).all(-1)
+    ok &= (~used[..., 1:] | (bucket[..., 1:] > bucket[..., :-1])).all(-1)
+    return ok
+
+
+def _chist_entries(elem: np.ndarray) -> dict:
+    """{bucket: count} of one canonical element (uint8 [64])."""
+    count, bucket, n = _chist_fields(elem)
+    n = int(n)
+    return dict(zip(bucket[:n].tolist(), count[:n].tolist()))
+
+
+def _chist_pack(entries: dict) -> np.ndarray:
+    e = np.zeros(CHIST_BYTES, np.uint8)
+    b = sorted(entries)
+    e[:4 * len(b)] = np.asarray([entries[x] for x in b], "<u4").view(np.uint8)
+    e[4 * CHIST_ENTRIES:4 * CHIST_ENTRIES + len(b)] = b
+    e[5 * CHIST_ENTRIES:] = np.asarray([len(b)], "<u4").view(np.uint8)
+    return e
+
+
+def _chist_update(entries: dict, c) -> tuple:
+    """UPDATE of one element ({bucket: count}) with the interval's counts ``c`` (240 ints): the
+    new entries and the number of folded samples (include/nvrx_straggler.h)."""
+    seen = [b for b, v in enumerate(c) if v > 0]
+    if not seen:
+        return dict(entries), 0
+    fresh = [b for b in seen if b not in entries]
+    kept = sorted(list(entries) + fresh[:CHIST_ENTRIES - len(entries)])
+    add = dict.fromkeys(kept, 0)
+    folded = 0
+    for b in seen:
+        below = [s for s in kept if s <= b]
+        add[below[-1] if below else kept[0]] += c[b]
+        if b not in add:
+            folded += c[b]
+    return {s: min(entries.get(s, 0) + add[s], 0xFFFFFFFF) for s in kept}, folded
+
+
+def compact_to_dense(chist) -> np.ndarray:
+    """The dense expansion (u32 [R, S, 240]) of a canonical compact history (uint8 [R, S, 64]):
+    ``H[bucket[i]] = count[i]`` for the used entries, zero elsewhere."""
+    c = _chist_array(chist)
+    if not compact_is_canonical(c).all():
+        raise ValueError("compact_to_dense: an element is not canonical")
+    count, bucket, n = _chist_fields(c)
+    H = np.zeros(c.shape[:2] + (BINS,), np.uint32)
+    for r, s, i in zip(*np.nonzero(np.arange(CHIST_ENTRIES) < n[..., None])):
+        H[r, s, bucket[r, s, i]] = count[r, s, i]
+    return H
+
+
+def compact_from_dense(hist) -> tuple:
+    """``(chist uint8 [R, S, 64], folded u64 [R])`` of a dense history ([R, S, 240]; int32 is read
+    as u32): by definition the UPDATE of an empty element with those counts -- the 12 lowest used
+    buckets are kept, the others folded into the highest kept one, ``folded`` their samples per
+    row."""
+    H = merge(hist)
+    if H.ndim != 3 or H.shape[2] != BINS:
+        raise ValueError(f"hist must have shape [R, S, {BINS}]")
+    out = np.zeros(H.shape[:2] + (CHIST_BYTES,), np.uint8)
+    folded = np.zeros(H.shape[0], np.uint64)
+    for r, s in zip(*np.nonzero(H.any(-1))):
+        entries, f = _chist_update({}, H[r, s].tolist())
+        out[r, s] = _chist_pack(entries)
+        folded[r] += np.uint64(f)
+    return out, folded
+
+
+@dataclass
+class CompactHistoryScores(HistoryScores):
+    """``compact_history_scores``: the fields of ``HistoryScores`` with ``hist`` the compact
+    history after the call (uint8 [R, S, 64]), and the samples UPDATE folded."""
+    folded: np.ndarray = None             # [R] u64 (None without update)
+
+
+def compact_history_scores(counts, chist, permille: int, *, score: bool = True, update: bool = True,
+                           hist_index=None, col_valid=None, skip_rows=None,
+                           score_thr: float = 0.75) -> CompactHistoryScores:
+    """``history_scores`` against a compact history ``chist`` (uint8 [R, S, 64], left unchanged;
+    the elements of the slots in use must be canonical): the score is ``history_scores``'s against
+    the dense expansion of every element; ``update`` admits an interval's new buckets in ascending
+    order while an element has free entries and folds every other sample into the nearest kept
+    bucket at or below it (the lowest kept one without any), ``folded`` counting them per row.
+    Only elements with samples in a row ``skip_rows`` does not mark change.  Python integers: the
+    host twin of ``ops.segment_history_scores_compact_ragged``."""
+    pm = _check_permille(permille)
+    if not (score or update):
+        raise ValueError("compact_history_scores: at least one of score and update")
+    c, ch = merge(counts), _chist_array(chist)
+    if c.ndim != 3 or c.shape[2] != BINS:
+        raise ValueError(f"counts must have shape [R, K, {BINS}]")
+    R, K, _ = c.shape
+    if ch.shape[0] != R:
+        raise ValueError(f"chist must have shape [R, S, {CHIST_BYTES}]")
+    S = ch.shape[1]
+    index = list(range(K)) if hist_index is None else [int(s) for s in np.asarray(hist_index)]
+    if len(index) != K or any(s >= S for s in index):
+        raise ValueError("hist_index must hold K slots below chist.shape[1]")
+    valid = [True] * K if col_valid is None else [bool(v) for v in np.asarray(col_valid)]
+    skip = [False] * R if skip_rows is None else [bool(v) for v in np.asarray(skip_rows)]
+    cols = [(k, s) for k, s in enumerate(index) if s >= 0 and valid[k]]
+    slots = sorted({s for _, s in cols})
+    if not compact_is_canonical(ch[:, slots]).all():
+        raise ValueError("compact_history_scores: an element of a slot in use is not canonical")
+    res = CompactHistoryScores(ch.copy())
+    if score:
+        H = np.zeros((R, S, BINS), np.uint32)
+        H[:, slots] = compact_to_dense(ch[:, slots])
+        d = history_scores(c, H, pm, update=False, hist_index=hist_index, col_valid=col_valid,
+                           score_thr=score_thr)
+        for f in ("score", "tail_ns", "total_ns", "base_tail_ns", "base_total_ns", "history_share",
+                  "stragglers", "threshold_bucket", "tail_calls"):
+            setattr(res, f, getattr(d, f))
+    if update:
+        folded = [0] * R
+        for r in range(R):
+            if skip[r]:
+                continue
+            for k, s in cols:
+                if c[r, k].any():
+                    entries, f = _chist_update(_chist_entries(ch[r, s]), c[r, k].tolist())
+                    res.hist[r, s] = _chist_pack(entries)
+                    folded[r] += f
+        res.folded = np.asarray([f & _M64 for f in folded], np.uint64).reshape(R)
+    return res
+
+
+def segment_compact_history_scores(keys, seg_off, seg_len, K: int, chist, permille: int,
+                                   cap: int = 0, **kwargs) -> CompactHistoryScores:
+    """Individual tail score per row straight from ragged segments of duration keys
+    (``segment_counts``'s addressing) against the rows' own compact history, the host twin of
+    ``ops.segment_history_scores_compact_ragged`` and of
+    ``MatrixReporter.individual_tail_scores_records(history="compact")``:
+    ``compact_history_scores`` (its keywords pass through) over the retained windows' counts."""
+    return compact_history_scores(segment_counts(keys, seg_off, seg_len, K, cap), chist, permille,
+                                  **kwargs)
 
 
 @dataclass

@@ -623,6 +623,80 @@ def segment_history_scores_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
                              out.base_total_ns, out.strag, calls)
 
 
+def segment_history_scores_compact_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
+                                          seg_len: Optional[torch.Tensor], K: int, max_len: int,
+                                          chist: torch.Tensor, *, permille: int, score: bool = True,
+                                          update: bool = True, cap: int = 0, aligned16: bool = False,
+                                          hist_index: Optional[torch.Tensor] = None,
+                                          hist_stride: int = 0,
+                                          col_valid: Optional[torch.Tensor] = None,
+                                          skip_rows: Optional[torch.Tensor] = None,
+                                          score_thr: float = 0.75, tail_calls=False,
+                                          out: Optional[HistoryTailScores] = None,
+                                          folded: Optional[torch.Tensor] = None, stream=None):
+    """``segment_history_scores_ragged`` against a compact history ``chist`` (uint8
+    [R, hist_stride or K, 64], changed in place): 64 bytes per (row, kernel) -- u32 count[12], u8
+    bucket[12], u32 n, the used buckets ascending -- in place of 960.  The score is the dense
+    entry's against the element's dense expansion; ``update`` admits an interval's new buckets in
+    ascending order while the element has free entries and folds every other sample into the
+    nearest kept bucket at or below it.  Returns ``(HistoryTailScores, folded)``: ``folded`` (int64
+    [R], u64 on the device; None without ``update``) counts the folded samples per row -- while it
+    stays 0 the history expands (``histograms.compact_to_dense``) to exactly the dense entry's and
+    every output equals that entry's bit for bit.  A zeroed ``chist`` is the empty history.  Every
+    other argument and ``out`` as in ``segment_history_scores_ragged``."""
+    pm = tail_permille(permille)
+    if not (score or update):
+        raise ValueError("segment_history_scores_compact_ragged: at least one of score and update")
+    R = _segment_rows(ns, seg_off, seg_len, K)
+    d = ns.device
+    stride = int(hist_stride)
+    if stride < 0 or (stride and hist_index is None and stride < K):
+        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
+    N.require_device(chist, "chist")
+    if chist.dtype != torch.uint8 or chist.data_ptr() % 16:
+        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor")
+    _tail_tensor(chist, "chist", torch.uint8, (R, stride or K, N.CHIST_BYTES))
+    if hist_index is not None:
+        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
+    _u8_vector(col_valid, "col_valid", K)
+    _u8_vector(skip_rows, "skip_rows", R)
+    calls = None
+    if score:
+        if out is None:
+            out = HistoryTailScores.empty(R, d)
+        _tail_tensor(out.score, "out.score", torch.float64, (R,))
+        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
+            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
+        if out.strag is not None:
+            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
+        if tail_calls is True:
+            calls = out.tail_calls
+            if calls is None:
+                calls = torch.empty((R, K), dtype=torch.int32, device=d)
+        elif tail_calls is not False and tail_calls is not None:
+            calls = tail_calls
+        if calls is not None:
+            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
+    elif out is None:
+        out = HistoryTailScores()
+    if update:
+        if folded is None:
+            folded = torch.empty(R, dtype=torch.int64, device=d)
+        _tail_tensor(folded, "folded", torch.int64, (R,))
+    else:
+        folded = None
+    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    a = N.SegCHistArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
+                       int(aligned16), chist.data_ptr(), stride, N.ptr(hist_index),
+                       N.ptr(col_valid), N.ptr(skip_rows), pm, mode, float(score_thr),
+                       N.ptr(out.tail_ns), N.ptr(out.total_ns), N.ptr(out.base_tail_ns),
+                       N.ptr(out.base_total_ns), N.ptr(out.score), N.ptr(out.strag), N.ptr(calls),
+                       N.ptr(folded))
+    N.call("nvrx_segment_history_scores_compact_ragged", ctypes.byref(a), _stream(stream))
+    return HistoryTailScores(out.score, out.tail_ns, out.total_ns, out.base_tail_ns,
+                             out.base_total_ns, out.strag, calls), folded
+
+
 def histogram_tail_base(fleet: torch.Tensor, thr: torch.Tensor, out: Optional[torch.Tensor] = None,
                         stream=None) -> torch.Tensor:
     """Per kernel of a fleet histogram (int64 [K, 240]) its weighted {tail, total} ns over the
