@@ -34,7 +34,7 @@
  * nvrx_histogram_tail_base / _tail_attribution, nvrx_segment_fleet_histogram_ragged,
  * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged,
  * nvrx_segment_history_scores_ragged, nvrx_segment_history_attribution_ragged,
- * nvrx_segment_history_scores_compact_ragged.
+ * nvrx_segment_history_scores_compact_ragged, nvrx_segment_history_attribution_compact_ragged.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -689,6 +689,51 @@ typedef struct nvrx_segchist_args {
     uint64_t* folded;           /* [R]; required with UPDATE */
 } nvrx_segchist_args;
 int nvrx_segment_history_scores_compact_ragged(const nvrx_segchist_args* args, void* stream);
+
+/* The individual tail score attribution of record streams against the compact history: what
+ * nvrx_segment_history_attribution_ragged is to the dense history.  No reference counterpart.
+ * nvrx_segchistattr_args has the fields of nvrx_seghistattr_args in the same order, with `const
+ * void* chist` ([R][hist_stride] elements of NVRX_CHIST_BYTES, read only) in the place of hist and
+ * hist_stride in elements.  By definition
+ *   nvrx_segment_history_attribution_compact_ragged  writes into idx, loss, tail_ns, total_ns,
+ *     tail_calls, thr_bucket, base_share ([R][top]) and loss_all ([R][K], written in full) what is
+ *     equal, bit for bit, to what nvrx_segment_history_attribution_ragged writes with hist the
+ *     dense expansion of chist (H[bucket[i]] = count[i] for i < n, zero elsewhere) and the same
+ *     segments, max_len, cap, aligned16, hist_index, col_valid, permille and top: an element
+ *     (r, k) is taken iff col_valid[k] != 0, its slot s >= 0, the element's N = sum of count > 0,
+ *     its retained length is > 0 and its loss is not NaN.
+ * Canonical input is assumed.  chist is READ ONLY here, and the content of the slots no column
+ * uses never influences an output: between a SCORE call and an UPDATE call of
+ * nvrx_segment_history_scores_compact_ragged the entry sees the history the score saw.  An element
+ * that is not valid, has no slot or an empty segment is not read.  Argument checks as for
+ * nvrx_segment_history_attribution_ragged, except that chist must be 16-byte aligned, the
+ * null-pointer message names chist and there is no K * 240 limit; R * K stays below 2^31.  R == 0
+ * or K == 0 launches nothing (outputs untouched).  Two kernels on `stream` only (every (r, k) has
+ * one owner): no allocation, no synchronisation, no host read-back, no scratch, no atomics, no
+ * clear; capturable as a linear chain with the calls around it. */
+typedef struct nvrx_segchistattr_args {
+    int64_t R, K;
+    const uint32_t* ns;         /* duration keys */
+    const int64_t* seg_off;     /* [R * K] (+ 1 without seg_len) */
+    const int32_t* seg_len;     /* [R * K] or NULL */
+    int64_t max_len, cap;
+    int32_t aligned16;          /* the caller's word that every retained run starts 16-byte aligned */
+    int32_t top;                /* 1..NVRX_MAX_ATTRIBUTION */
+    const void* chist;          /* [R][hist_stride] elements of NVRX_CHIST_BYTES, read only */
+    int64_t hist_stride;        /* in elements; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* [K] or NULL */
+    int32_t permille;
+    int32_t* idx;               /* [R][top] */
+    double* loss;               /* [R][top] */
+    uint64_t* tail_ns;          /* [R][top] */
+    uint64_t* total_ns;         /* [R][top] */
+    uint32_t* tail_calls;       /* [R][top] */
+    int32_t* thr_bucket;        /* [R][top] */
+    double* base_share;         /* [R][top] */
+    double* loss_all;           /* [R][K] */
+} nvrx_segchistattr_args;
+int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

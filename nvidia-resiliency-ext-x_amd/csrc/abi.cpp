@@ -6,8 +6,8 @@
 // nvrx_cupti_module.CuptiProfiler lives in profiler.cpp.  All arithmetic runs in the HIP
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
 // histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip,
-// segment_tail_attribution.hip, segment_history.hip, segment_history_attribution.hip and
-// records.hip.
+// segment_tail_attribution.hip, segment_history.hip, segment_history_attribution.hip,
+// segment_history_compact.hip, segment_history_compact_attribution.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -579,6 +579,45 @@ int nvrx_segment_history_attribution_ragged(const nvrx_seghistattr_args* a, void
     NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
     return hip_status(nvrx::segment_history_attribution_ragged(*a, S(stream)), fn.c_str());
+}
+
+// the same attribution against the compact history (segment_history_compact_attribution.hip):
+// the checks above without the K * 240 limit, which belongs to the dense history
+int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args* a, void* stream) {
+    const std::string fn("nvrx_segment_history_attribution_compact_ragged");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
+                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    NVRX_CHECK_ARG(a->R >= 0, fn + ": negative R");
+    NVRX_CHECK_ARG(a->K >= 0, fn + ": negative K");
+    NVRX_CHECK_ARG(a->R == 0 || a->K <= (((int64_t)1 << 31) - 1) / a->R,
+                   fn + ": R * K must be below 2^31");
+    if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
+                              a->max_len, a->cap))
+        return rc;
+    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                   fn + ": hist_stride below K without hist_index");
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->chist, fn + ": null chist");
+        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
+        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
+        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
+        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
+        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
+        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->chist & 15) == 0, fn + ": chist not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
+    return hip_status(nvrx::segment_history_attribution_compact_ragged(*a, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

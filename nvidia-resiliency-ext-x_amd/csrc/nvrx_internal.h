@@ -67,6 +67,9 @@ hipError_t segment_history_attribution_ragged(const nvrx_seghistattr_args& a, hi
 // individual tail scores straight from those segments against a compact history
 // (segment_history_compact.hip)
 hipError_t segment_history_scores_compact_ragged(const nvrx_segchist_args& a, hipStream_t st);
+// the individual tail score attribution against that compact history
+// (segment_history_compact_attribution.hip)
+hipError_t segment_history_attribution_compact_ragged(const nvrx_segchistattr_args& a, hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

@@ -1,0 +1,398 @@
+// segment_history_compact_attribution.hip -- individual tail score attribution straight from
+// ragged segments against a compact history, on gfx950.
+//
+// No reference counterpart.  segment_history_attribution.hip names the kernels behind an
+// individual tail score from the bucketed samples and the dense history of 960 B per (rank,
+// kernel); segment_history_compact.hip scores against a compact history of 64 B per element
+// (include/nvrx_straggler.h, "compact history": u32 count[12], u8 bucket[12], u32 n).  This file
+// attributes against that compact history.  By definition every output is what
+// nvrx_segment_history_attribution_ragged writes with hist the dense expansion of chist
+// (H[bucket[i]] = count[i] for i < n, zero elsewhere): per (rank r, kernel k) with slot s,
+//     T      = the bucket of the entry that holds the history's sample of rank (pm (N - 1)) / 1000
+//     btail  = sum_{i : bucket[i] > T} count[i] w(bucket[i])    btotal = sum_i count[i] w(bucket[i])
+//     tail   = sum_{x : bucket(x) > T} w(bucket(x))             total  = sum_x w(bucket(x))
+//     loss   = tail - total * (btail / btotal)                                      (f64, ns)
+// integer sums plus three f64 operations.  chist is read only.  Two kernels:
+//
+//   segchist_loss_kernel    grid (rows, splits of K), 256 threads, the split rule and the
+//          16-element workgroup trip of segchist_kernel / seghist_loss_kernel.  A wave takes the
+//          SCA_UNROLL = 4 consecutive kernels from k0 + 4 wave, so that their losses are
+//          neighbours in loss_all, and loads their elements with ONE instruction: DPP row u
+//          (lanes 16u..16u+15) holds element u, one dword per lane -- lanes 0..11 a count, 12..14
+//          the bucket bytes, 15 n; the row's address comes from its own slot.  A row whose kernel
+//          is >= K, not valid, without a slot or whose segment is empty is not loaded (its word is
+//          0: the empty history).  Inside the rows, side by side for the four elements
+//          (rows_base): a bpermute hands each count lane its bucket byte; the u64 row_shr prefix
+//          gives N in the row's last lane and the rank by the 64-bit split; a ballot gives the
+//          entry that holds the rank and a readlane its bucket T; count * weight_of(bucket) per
+//          lane, reduced in the row by four DPP steps, gives btotal and btail.  The retained run
+//          is walked as in segment_history_attribution.hip (walk): 64 samples per load, SCA_LOADS
+//          loads in flight, a lane past the end masked, per-lane u64 tail / total.  The partial
+//          sums of the four elements are kept until all their samples are read; then their u64
+//          wave reductions stand next to each other as independent DPP chains, the three f64
+//          operations finish each loss, lane u keeps the loss of element u and lanes 0..3 store
+//          the trip's losses with one 32-byte store.  NaN where the element is not taken:
+//          loss_all is written in full, no clear.
+//   segchist_select_kernel  one 256-thread workgroup per row over loss_all[r][:]: the scheme of
+//          seghist_select_kernel (topk_select.h).  Then wave v recomputes winners v, v + 4, ...
+//          from the winner's 64-byte element (row 0 of rows_base, the other rows empty) and its
+//          samples with the same two functions and `excess`, the calls from a ballot and a
+//          population count, and lane 0 stores every per-winner output.  What is stored comes
+//          from the inputs, the key only orders.
+// Every (r, k) has one owner: no atomics, no scratch, no clear, no LDS in the loss kernel.
+// bucket_of, row_incl_scan_u64, the masked sample load and `excess` restate what
+// segment_history_compact.hip and segment_history_attribution.hip hold in their anonymous
+// namespaces; no existing file changes.  Every loop is bounded by K or a retained length (an
+// element's 12 entries are lanes, not iterations).  No kernel uses scratch memory (make asm;
+// DESIGN 3.19).
+
+#include <type_traits>
+
+#include "histogram_wave.h"
+#include "segment_addr.h"
+#include "topk_select.h"
+
+namespace nvrx {
+namespace {
+
+constexpr int SCA_THREADS = 256;
+constexpr int SCA_WAVES = SCA_THREADS / 64;
+constexpr int SCA_UNROLL = 4;                      // elements per wave trip: one per DPP row
+constexpr int SCA_TRIP = SCA_WAVES * SCA_UNROLL;   // elements per workgroup trip: a split's granule
+constexpr int SCA_TARGET_WGS = 2048;               // 256 CUs x 8 workgroups
+constexpr int SCA_LOADS = 4;                       // sample loads in flight per lane
+constexpr int SCA_E = NVRX_CHIST_ENTRIES;
+constexpr int SCA_WORDS = NVRX_CHIST_BYTES / 4;    // 16: one DPP row
+static_assert(SCA_WORDS == 16 && SCA_UNROLL * SCA_WORDS == NVRX_WAVE, "an element is one DPP row");
+static_assert(4 * SCA_E + SCA_E + 4 == NVRX_CHIST_BYTES, "count[12], bucket[12], n");
+
+// segment_histogram.hip's bucket expression: sh = e - 3 for x >= 8, 0 below
+__device__ __forceinline__ unsigned bucket_of(unsigned x) {
+    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
+    return (sh << 3) + (x >> sh);
+}
+
+// inclusive u64 prefix inside each 16-lane row (row_shr zero-fills at the row's start)
+__device__ __forceinline__ u64 row_incl_scan_u64(u64 v) {
+    v += dpp_u64<0x111>(v);
+    v += dpp_u64<0x112>(v);
+    v += dpp_u64<0x114>(v);
+    v += dpp_u64<0x118>(v);
+    return v;
+}
+
+// the sum of each 16-lane row in every lane of the row: the DPP steps of wave_sum_u64
+__device__ __forceinline__ u64 row_sum_u64(u64 v) {
+    v += dpp_u64<0xB1>(v);
+    v += dpp_u64<0x4E>(v);
+    v += dpp_u64<0x141>(v);
+    v += dpp_u64<0x140>(v);
+    return v;
+}
+
+// a wave-uniform value per row, picked by the lane's row
+template <typename T>
+__device__ __forceinline__ T by_row(int row, T v0, T v1, T v2, T v3) {
+    return row == 0 ? v0 : row == 1 ? v1 : row == 2 ? v2 : v3;
+}
+
+// What four elements' histories give, side by side: btail / btotal are the row's sums (in every
+// lane of row u for element u); T and elig (N > 0) are wave-uniform.
+struct RowBase {
+    u64 btail, btotal;
+    int T[SCA_UNROLL];
+    bool elig[SCA_UNROLL];
+};
+
+// word: row u, lane j holds dword j of element u (zero: the empty history)
+__device__ __forceinline__ RowBase rows_base(unsigned word, int pm, int lane) {
+    const int row = lane >> 4, j = lane & 15;
+    // lanes 0..11 of a row: the entry's count and bucket (zero beyond n, by the canonical form)
+    const unsigned bytes = (unsigned)__builtin_amdgcn_ds_bpermute(4 * ((lane & 48) + SCA_E + (j >> 2)),
+                                                                  (int)word);
+    const bool entry = j < SCA_E;
+    const unsigned cnt = entry ? word : 0u;
+    const unsigned bkt = entry ? (bytes >> (8 * (j & 3))) & 0xFFu : 0u;
+    const u64 incl = row_incl_scan_u64((u64)cnt);
+    // lanes 12..15 add nothing: the row's last lane holds N
+    const u64 n0 = rl_u64(incl, 15), n1 = rl_u64(incl, 31), n2 = rl_u64(incl, 47), n3 = rl_u64(incl, 63);
+    const u64 N = by_row(row, n0, n1, n2, n3);
+    // (pm (N - 1)) / 1000 without the product leaving 64 bits (N == 0: no rank, nothing below it)
+    const u64 N1 = N ? N - 1 : 0ull;
+    const u64 d = N1 / 1000ull, mm = N1 % 1000ull;
+    const u64 rank = (u64)pm * d + ((u64)pm * mm) / 1000ull;
+    // incl is non-decreasing over the row and incl[11] = N > rank: the entries at or below rank
+    // are a prefix, and the entry after them has a count
+    const uint64_t below = __ballot(entry && N != 0 && incl <= rank);
+    RowBase b;
+    b.elig[0] = n0 != 0;
+    b.elig[1] = n1 != 0;
+    b.elig[2] = n2 != 0;
+    b.elig[3] = n3 != 0;
+#pragma unroll
+    for (int u = 0; u < SCA_UNROLL; ++u) {
+        const int L = __builtin_popcount((unsigned)(below >> (16 * u)) & 0xFFFFu);  // <= 11
+        b.T[u] = b.elig[u] ? (int)rl(bkt, 16 * u + L) : -1;
+    }
+    const int t = by_row(row, b.T[0], b.T[1], b.T[2], b.T[3]);
+    const u64 wsum = (u64)cnt * weight_of((int)bkt);
+    b.btotal = row_sum_u64(wsum);
+    b.btail = row_sum_u64((int)bkt > t ? wsum : 0ull);
+    return b;
+}
+
+// One element's samples before the wave reductions: the lane's part of tail / total over the
+// retained run q of m > 0 samples against the threshold bucket t.  CALLS adds the count above t.
+struct Walk {
+    u64 tail, total;
+    unsigned calls;
+};
+template <bool CALLS>
+__device__ __forceinline__ Walk walk(const uint32_t* q, int m, int t, int lane) {
+    Walk p = {0ull, 0ull, 0u};
+    for (int base = 0; base < m; base += 64 * SCA_LOADS) {
+        unsigned x[SCA_LOADS];
+#pragma unroll
+        for (int v = 0; v < SCA_LOADS; ++v) {
+            const int i = base + v * 64 + lane;
+            x[v] = i < m ? __builtin_nontemporal_load(q + i) : 0u;
+        }
+#pragma unroll
+        for (int v = 0; v < SCA_LOADS; ++v) {
+            if (base + v * 64 >= m) break;  // wave-uniform
+            const bool live = base + v * 64 + lane < m;
+            const unsigned b = bucket_of(x[v]);
+            const u64 wt = live ? (u64)weight_of((int)b) : 0ull;
+            const bool hit = live && (int)b > t;
+            p.total += wt;
+            p.tail += hit ? wt : 0ull;
+            if (CALLS) p.calls += (unsigned)__popcll(__ballot(hit));
+        }
+    }
+    return p;
+}
+
+// the three f64 operations of the definition, each rounded separately (-ffp-contract=off): both
+// kernels call it, so a winner's stored loss is the loss that ranked it
+__device__ __forceinline__ double excess(u64 tail, u64 total, u64 btail, u64 btotal, double& share) {
+    share = (double)btail / (double)btotal;
+    return (double)tail - (double)total * share;
+}
+
+// slot of column k (wave-uniform), -1 where the column is not eligible
+__device__ __forceinline__ int64_t slot_of(const nvrx_segchistattr_args& a, int64_t k) {
+    int64_t s = a.hist_index ? (int64_t)a.hist_index[k] : k;
+    if (a.col_valid && !a.col_valid[k]) s = -1;
+    return s;
+}
+
+// kernels [blockIdx.y * kper, + kper) of row blockIdx.x
+__global__ __launch_bounds__(SCA_THREADS)
+void segchist_loss_kernel(RaggedSegs segs, nvrx_segchistattr_args a, int64_t kper) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = lane_id();
+    const int row = lane >> 4, j = lane & 15;  // the element of the trip this lane holds a word of
+    const int64_t r = blockIdx.x;
+    const int64_t K = a.K;
+    const int64_t kb = (int64_t)blockIdx.y * kper;
+    const int64_t ke = min(K, kb + kper);
+    const int64_t stride = a.hist_stride ? a.hist_stride : K;
+    const unsigned* const crow = (const unsigned*)a.chist + r * stride * SCA_WORDS;
+    double* const out = a.loss_all + r * K;
+    const int pm = a.permille;
+    const double qnan = __builtin_nan("");
+    for (int64_t k0 = kb + wave * SCA_UNROLL; k0 < ke; k0 += SCA_TRIP) {  // wave-uniform
+        int64_t slot[SCA_UNROLL];
+        const uint32_t* run[SCA_UNROLL];
+        int len[SCA_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SCA_UNROLL; ++u) {
+            const int64_t k = k0 + u;  // wave-uniform, and so is all that follows from it
+            slot[u] = -1;
+            run[u] = nullptr;
+            len[u] = 0;
+            if (k < ke) {
+                int64_t s = slot_of(a, k);
+                if (s >= 0) segs.get(r * K + k, run[u], len[u]);
+                if (len[u] <= 0) {  // an empty element: no loss, no read of the history
+                    len[u] = 0;
+                    s = -1;
+                }
+                slot[u] = s;
+            }
+        }
+        // the trip's four elements in one load: row u, word j
+        const int64_t sl = by_row(row, slot[0], slot[1], slot[2], slot[3]);
+        const unsigned word = sl >= 0 ? crow[sl * SCA_WORDS + j] : 0u;
+        const RowBase base = rows_base(word, pm, lane);
+        Walk p[SCA_UNROLL];
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < SCA_UNROLL; ++u) {
+            p[u] = Walk{0ull, 0ull, 0u};
+            if (base.elig[u]) p[u] = walk<false>(run[u], len[u], base.T[u], lane);  // len > 0
+            any |= base.elig[u];
+        }
+        double loss = qnan;
+        if (any) {  // wave-uniform; the reductions are independent of each other
+#pragma unroll
+            for (int u = 0; u < SCA_UNROLL; ++u) {
+                const u64 tail = wave_sum_u64(p[u].tail), total = wave_sum_u64(p[u].total);
+                const u64 bl = rl_u64(base.btail, 16 * u), bt = rl_u64(base.btotal, 16 * u);
+                double share;
+                const double v = excess(tail, total, bl, bt, share);
+                if (lane == u) loss = base.elig[u] && v == v ? v : qnan;
+            }
+        }
+        if (lane < SCA_UNROLL && k0 + lane < ke) out[k0 + lane] = loss;
+    }
+}
+
+template <int TOP>
+__global__ __launch_bounds__(256)
+void segchist_select_kernel(RaggedSegs segs, nvrx_segchistattr_args a) {
+    __shared__ uint64_t best_k[2][4];
+    __shared__ int32_t best_c[2][4];
+    __shared__ int32_t win[NVRX_MAX_ATTRIBUTION];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int64_t r = blockIdx.x;
+    const int64_t K = a.K;
+    const double* __restrict__ row = a.loss_all + r * K;
+
+    // this thread's candidates, best first; every index below is a compile-time constant
+    uint64_t ck[TOP];
+    int32_t cc[TOP];
+#pragma unroll
+    for (int i = 0; i < TOP; ++i) {
+        ck[i] = 0;
+        cc[i] = NO_COL;
+    }
+    constexpr int SC = 8;  // every load of a batch is issued before any is used
+    // FIRST: the thread's first batch, whose element c finds at most c candidates held
+    auto batch = [&](const int64_t k0, auto first) {
+        constexpr bool FIRST = decltype(first)::value;
+        double v[SC];
+#pragma unroll
+        for (int c = 0; c < SC; ++c) {
+            const int64_t k = k0 + c * 256;
+            v[c] = k < K ? row[k] : __builtin_nan("");
+        }
+#pragma unroll
+        for (int c = 0; c < SC; ++c) {
+            const uint64_t key = v[c] == v[c] ? loss_key(v[c]) : 0ull;  // NaN: not taken
+            const int32_t col = (int32_t)(k0 + c * 256);
+            const int n = FIRST && c + 1 < TOP ? c + 1 : TOP;  // positions from n on are empty
+            if (__builtin_amdgcn_ballot_w64(key > ck[n - 1]) == 0) continue;  // wave-uniform skip
+            NVRX_TOPK_INSERT(TOP, ck, cc, key, col, n);
+        }
+    };
+    batch(tid, std::true_type{});
+    for (int64_t k0 = (int64_t)tid + 256 * SC; k0 < K; k0 += 256 * SC) batch(k0, std::false_type{});
+
+    // `top` rounds of workgroup argmax over the threads' heads
+    const int top = a.top < TOP ? a.top : TOP;
+    for (int j = 0; j < top; ++j) {
+        uint64_t k = ck[0];
+        int32_t c = cc[0];
+        wave_best(k, c);
+        const int b = j & 1;
+        if (lane == 0) {
+            best_k[b][wave] = k;
+            best_c[b][wave] = c;
+        }
+        __syncthreads();
+        uint64_t wk = best_k[b][0];
+        int32_t wc = best_c[b][0];
+#pragma unroll
+        for (int v = 1; v < 4; ++v) {
+            const uint64_t ok = best_k[b][v];
+            const int32_t oc = best_c[b][v];
+            const bool take = before(ok, oc, wk, wc);
+            wk = take ? ok : wk;
+            wc = take ? oc : wc;
+        }
+        if (tid == 0) win[j] = wk != 0 ? wc : -1;
+        // the winner pops its head (columns are distinct, so one thread at most holds wc); the
+        // three waves without it skip the shift
+        const bool pop = wk != 0 && cc[0] == wc;
+        if (__builtin_amdgcn_ballot_w64(pop) == 0) continue;
+        NVRX_TOPK_POP(TOP, ck, cc, pop);
+    }
+    __syncthreads();
+
+    // wave v recomputes winners v, v + 4, ... from the element and the samples and stores their
+    // outputs
+    const int64_t stride = a.hist_stride ? a.hist_stride : K;
+    const unsigned* const crow = (const unsigned*)a.chist + r * stride * SCA_WORDS;
+    for (int j = wave; j < top; j += 4) {
+        const int col = __builtin_amdgcn_readfirstlane(win[j]);
+        u64 tail = 0, total = 0;
+        unsigned calls = 0;
+        int T = -1;
+        double share = __builtin_nan(""), loss = share;
+        if (col >= 0) {  // wave-uniform, as everything up to the stores
+            const int64_t s = slot_of(a, (int64_t)col);
+            const uint32_t* q = nullptr;
+            int m = 0;
+            if (s >= 0) segs.get(r * K + col, q, m);
+            if (m > 0) {
+                // the winner's element in row 0, the empty history in the other rows
+                const unsigned word = lane < SCA_WORDS ? crow[s * SCA_WORDS + lane] : 0u;
+                const RowBase base = rows_base(word, a.permille, lane);
+                if (base.elig[0]) {
+                    const Walk p = walk<true>(q, m, base.T[0], lane);
+                    tail = wave_sum_u64(p.tail);
+                    total = wave_sum_u64(p.total);
+                    const u64 bl = rl_u64(base.btail, 0), bt = rl_u64(base.btotal, 0);
+                    calls = p.calls;
+                    T = base.T[0];
+                    loss = excess(tail, total, bl, bt, share);
+                }
+            }
+        }
+        if (lane != 0) continue;
+        const bool taken = loss == loss;
+        const int64_t o = r * a.top + j;
+        const double qnan = __builtin_nan("");
+        a.idx[o] = taken ? col : -1;
+        a.loss[o] = taken ? loss : qnan;
+        a.tail_ns[o] = taken ? tail : 0ull;
+        a.total_ns[o] = taken ? total : 0ull;
+        a.tail_calls[o] = taken ? calls : 0u;
+        a.thr_bucket[o] = taken ? T : -1;
+        a.base_share[o] = taken ? share : qnan;
+    }
+}
+
+}  // namespace
+
+// Argument checks happen in abi.cpp before this runs.
+hipError_t segment_history_attribution_compact_ragged(const nvrx_segchistattr_args& a, hipStream_t st) {
+    if (a.R <= 0 || a.K <= 0) return hipSuccess;
+    if (a.top < 1 || a.top > NVRX_MAX_ATTRIBUTION) return hipErrorInvalidValue;
+    // the split rule of segment_history_scores_compact_ragged: about SCA_TARGET_WGS workgroups
+    // over rows x splits, a split no shorter than one workgroup trip (SCA_TRIP kernels) and a
+    // whole number of trips
+    int64_t splits = (SCA_TARGET_WGS + a.R - 1) / a.R;
+    splits = min(splits, (a.K + SCA_TRIP - 1) / SCA_TRIP);
+    int64_t kper = (a.K + splits - 1) / splits;
+    kper = (kper + SCA_TRIP - 1) / SCA_TRIP * SCA_TRIP;
+    splits = (a.K + kper - 1) / kper;  // <= SCA_TARGET_WGS: fits grid.y
+    const dim3 grid((unsigned)a.R, (unsigned)splits);
+    const dim3 rows((unsigned)a.R), b(256);
+    const RaggedSegs segs{a.ns, a.seg_off, a.seg_len, a.cap};
+    hipLaunchKernelGGL(segchist_loss_kernel, grid, dim3(SCA_THREADS), 0, st, segs, a, kper);
+    if (a.top <= 1)
+        hipLaunchKernelGGL(segchist_select_kernel<1>, rows, b, 0, st, segs, a);
+    else if (a.top <= 4)
+        hipLaunchKernelGGL(segchist_select_kernel<4>, rows, b, 0, st, segs, a);
+    else if (a.top <= 8)
+        hipLaunchKernelGGL(segchist_select_kernel<8>, rows, b, 0, st, segs, a);
+    else
+        hipLaunchKernelGGL(segchist_select_kernel<16>, rows, b, 0, st, segs, a);
+    return hipGetLastError();
+}
+
+}  // namespace nvrx

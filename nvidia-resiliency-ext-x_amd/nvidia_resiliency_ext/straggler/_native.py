@@ -150,6 +150,16 @@ class SegHistAttrArgs(ctypes.Structure):
     ]
 
 
+class SegCHistAttrArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("ns", P), ("seg_off", P), ("seg_len", P), ("max_len", i64),
+        ("cap", i64), ("aligned16", i32), ("top", i32), ("chist", P), ("hist_stride", i64),
+        ("hist_index", P), ("col_valid", P), ("permille", i32),
+        ("idx", P), ("loss", P), ("tail_ns", P), ("total_ns", P), ("tail_calls", P),
+        ("thr_bucket", P), ("base_share", P), ("loss_all", P),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -203,6 +213,8 @@ SIGNATURES = {
     "nvrx_segment_history_scores_ragged": (ctypes.c_int, [ctypes.POINTER(SegHistArgs), P]),
     "nvrx_segment_history_attribution_ragged": (ctypes.c_int, [ctypes.POINTER(SegHistAttrArgs), P]),
     "nvrx_segment_history_scores_compact_ragged": (ctypes.c_int, [ctypes.POINTER(SegCHistArgs), P]),
+    "nvrx_segment_history_attribution_compact_ragged": (ctypes.c_int,
+                                                        [ctypes.POINTER(SegCHistAttrArgs), P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

@@ -483,10 +483,12 @@ class MatrixReporter:
                                BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
                                if top else None)
 
-    def _records_tail_work(self, n: int) -> dict:
+    def _records_tail_work(self, n: int, owner: str) -> dict:
         """The tail work tensors of the record-stream methods (``tail_scores_records``,
         ``individual_tail_scores_records``), allocated at first use, the bucketing scratch grown to
-        hold ``n`` records."""
+        hold ``n`` records.  ``owner`` names the path that is about to bucket into them:
+        ``compact_tail_attribution`` reads the buckets later and must know they are still the
+        compact call's."""
         R, K, d = self.R, self.K, self.device
         if self._rtail is None:
             # packed as tail_scores packs:
@@ -494,8 +496,9 @@ class MatrixReporter:
             kp = (K + 1) // 2 * 2
             self._rtail = dict(buf=torch.zeros(8 * (3 * R + 2) + 4 * kp + R, dtype=torch.uint8, device=d),
                                fleet=torch.empty((K, histograms.BINS), dtype=torch.int64, device=d),
-                               calls=None, kp=kp, bucket=None)
+                               calls=None, kp=kp, bucket=None, owner=None)
         t = self._rtail
+        t["owner"] = owner
         need = ops.records_bucket_capacity(n, R, K)
         if t["bucket"] is None or t["bucket"][2].numel() < need:
             t["bucket"] = (torch.empty(R * K, dtype=torch.int64, device=d),
@@ -544,7 +547,7 @@ class MatrixReporter:
         if rec_off.numel() != R + 1:
             raise ValueError(f"rec_off must hold {R + 1} offsets")
         self._order_after_inflight()
-        t = self._records_tail_work(recs.shape[0])
+        t = self._records_tail_work(recs.shape[0], "relative")
         kp, buf = t["kp"], t["buf"]
         n = recs.shape[0]
         base_len = buf.numel()
@@ -703,8 +706,10 @@ class MatrixReporter:
         below; ``.folded`` (u64 [R], in the same device-to-host copy) counts the samples folded in
         this call, and while it stays 0 every result equals ``history="dense"``'s bit for bit
         (``histograms.segment_compact_history_scores`` on the host).  ``attribute`` is not
-        available against the compact history yet (NotImplementedError).  ``history="dense"``
-        (default) is the path described above, untouched.  Beyond the reference."""
+        taken together with the compact history (NotImplementedError): ask
+        ``compact_tail_attribution()`` after this call, which explains it on request.
+        ``history="dense"`` (default) is the path described above, untouched.  Beyond the
+        reference."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
@@ -715,14 +720,15 @@ class MatrixReporter:
             raise NotImplementedError("MatrixReporter.individual_tail_scores_records: tail scores "
                                       "across kernel shards (exchange=True) are not supported")
         if history == "compact" and top:
-            raise NotImplementedError("MatrixReporter.individual_tail_scores_records: attribution "
-                                      "against the compact history is not supported")
+            raise NotImplementedError("MatrixReporter.individual_tail_scores_records: attribute= "
+                                      "is not available with the compact history; call "
+                                      "compact_tail_attribution() after the scores")
         R, K, d = self.R, self.K, self.device
         if rec_off.numel() != R + 1:
             raise ValueError(f"rec_off must hold {R + 1} offsets")
         self._order_after_inflight()
         n = recs.shape[0]
-        w = self._records_tail_work(n)
+        w = self._records_tail_work(n, history)
         if history == "compact":
             return self._individual_tail_scores_records_compact(recs, rec_off, w, pm, threshold,
                                                                 absorb, tail_calls)
@@ -787,6 +793,7 @@ class MatrixReporter:
         n = recs.shape[0]
         seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=w["bucket"])
         max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
+        w["compact_call"] = (seg_off, seg_len, out_ns, max_len, pm)  # for compact_tail_attribution
         res, _ = ops.segment_history_scores_compact_ragged(
             out_ns, seg_off, seg_len, K, max_len, t["chist"], permille=pm,
             update=absorb == "always", aligned16=True, col_valid=self.col_valid,
@@ -812,6 +819,50 @@ class MatrixReporter:
         [R, K, 64] on the device; ``histograms.compact_to_dense`` expands a host copy), or None
         before its first use."""
         return None if self._ctail is None else self._ctail["chist"]
+
+    def compact_tail_attribution(self, top: int = 8, *,
+                                 permille: Optional[int] = None) -> BatchTailAttribution:
+        """The kernels behind the individual tail scores against the compact history, on request
+        (as ``attribute()`` explains the last report): per rank the `top` (1..16) kernels with the
+        largest excess tail time ``tail - total * history_share_k`` in ns, for the buckets the
+        reporter's last ``individual_tail_scores_records(history="compact")`` call laid out,
+        against the compact history AS IT STANDS when this method runs
+        (``ops.segment_history_attribution_compact_ragged``;
+        ``histograms.segment_compact_history_attribution`` on the host).  ``permille=None`` means
+        that call's permille.  For every rank that call did not absorb -- the flagged ranks under
+        the default ``absorb="healthy"``, every rank under ``"never"``: the ranks one asks about --
+        this is the history the score saw, and the result equals, bit for bit, what
+        ``individual_tail_scores_records(attribute=top)`` gives against the dense history while
+        nothing was folded.  For a rank the call absorbed (healthy ranks under ``"healthy"``, every
+        rank under ``"always"``) it is the UPDATED history, the interval included.  The method
+        does not bucket again, touches no report buffer and leaves the history bit-identical; it
+        queues behind reports in flight, and the results come in one device-to-host copy
+        (``loss_all`` stays on the device).  RuntimeError if no compact record-stream call has run,
+        or if another record-stream method has re-used the bucketing work tensors since.  Beyond
+        the reference."""
+        top, _ = ops.attribution_request(top, "individual")
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.compact_tail_attribution: tail scores across "
+                                      "kernel shards (exchange=True) are not supported")
+        w, t = self._rtail, self._ctail
+        if t is None or w is None or w.get("compact_call") is None:
+            raise RuntimeError("MatrixReporter.compact_tail_attribution: no "
+                               "individual_tail_scores_records(history=\"compact\") call to explain")
+        if w["owner"] != "compact":
+            raise RuntimeError("MatrixReporter.compact_tail_attribution: another record-stream "
+                               "method has re-used the buckets of the last compact call")
+        seg_off, seg_len, out_ns, max_len, pm = w["compact_call"]
+        if permille is not None:
+            pm = ops.tail_permille(permille)
+        R, K = self.R, self.K
+        self._order_after_inflight()
+        aoff = self._tail_attr_buffers(t, 0)
+        buf = t["abuf"][aoff:aoff + ops.TailAttribution.PACKED * R * top]
+        ops.segment_history_attribution_compact_ragged(
+            out_ns, seg_off, seg_len, K, max_len, t["chist"], permille=pm, top=top, aligned16=True,
+            col_valid=self.col_valid, out=ops.TailAttribution.packed(buf, R, top, t["loss_all"]))
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        return BatchTailAttribution.unpack(host, R, top, t["loss_all"])
 
     def reset_tail_history(self) -> None:
         """Forget the histories of ``individual_tail_scores`` (dense and compact): the next

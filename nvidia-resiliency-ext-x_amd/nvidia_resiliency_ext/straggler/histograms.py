@@ -34,7 +34,10 @@ from ragged segments, without the counts (``ops.segment_fleet_histogram_ragged``
 ``compact_history_scores`` / ``segment_compact_history_scores`` are the host side of the compact
 history (64 bytes per rank and kernel: at most 12 used buckets, further ones folded downwards;
 ``ops.segment_history_scores_compact_ragged``,
-``MatrixReporter.individual_tail_scores_records(history="compact")``).
+``MatrixReporter.individual_tail_scores_records(history="compact")``), and
+``compact_history_attribution`` / ``segment_compact_history_attribution`` of the attribution
+against it (``ops.segment_history_attribution_compact_ragged``,
+``MatrixReporter.compact_tail_attribution``).
 """
 from __future__ import annotations
 
@@ -665,6 +668,69 @@ def segment_history_attribution(keys, seg_off, seg_len, K: int, hist, permille: 
     the retained windows' counts."""
     return history_attribution(segment_counts(keys, seg_off, seg_len, K, cap), hist, permille, top,
                                hist_index, col_valid)
+
+
+def compact_history_attribution(counts, chist, permille: int, top: int, hist_index=None,
+                                col_valid=None) -> TailAttribution:
+    """``history_attribution`` against a compact history ``chist`` (uint8 [R, S, 64], read only;
+    the elements of the slots in use must be canonical): by definition its result on the dense
+    expansion of every element, worked out here from the element's at most 12 entries directly --
+    N their counts' sum, T the bucket of the first entry whose running count passes the rank
+    ``(permille * (N - 1)) // 1000``, the base sums ``count * weight`` over the entries / those
+    above T.  The content of slots no column uses is not looked at.  Python integers: the host
+    twin of ``ops.segment_history_attribution_compact_ragged``."""
+    pm = _check_permille(permille)
+    c, ch = merge(counts), _chist_array(chist)
+    if c.ndim != 3 or c.shape[2] != BINS:
+        raise ValueError(f"counts must have shape [R, K, {BINS}]")
+    R, K, _ = c.shape
+    if ch.shape[0] != R:
+        raise ValueError(f"chist must have shape [R, S, {CHIST_BYTES}]")
+    S = ch.shape[1]
+    index = list(range(K)) if hist_index is None else [int(s) for s in np.asarray(hist_index)]
+    if len(index) != K or any(s >= S for s in index):
+        raise ValueError("hist_index must hold K slots below chist.shape[1]")
+    valid = [True] * K if col_valid is None else [bool(v) for v in np.asarray(col_valid)]
+    slots = sorted({s for k, s in enumerate(index) if s >= 0 and valid[k]})
+    if not compact_is_canonical(ch[:, slots]).all():
+        raise ValueError("compact_history_attribution: an element of a slot in use is not canonical")
+    count, bucket, used = (x.tolist() for x in _chist_fields(ch))
+    w = weights()
+
+    def element(r, k):
+        s = index[k]
+        if s < 0 or not valid[k]:
+            return None
+        n = used[r][s]
+        cnt, bkt = count[r][s][:n], bucket[r][s][:n]
+        N = sum(cnt)
+        cur = c[r, k].tolist()
+        if N == 0 or not any(cur):
+            return None
+        rank, acc = (pm * (N - 1)) // 1000, 0
+        for v, t in zip(cnt, bkt):
+            acc += v
+            if acc > rank:
+                break
+        btotal = sum(v * w[b] for v, b in zip(cnt, bkt)) & _M64
+        btail = sum(v * w[b] for v, b in zip(cnt, bkt) if b > t) & _M64
+        tail, total, calls = _wsums(cur, t, w)
+        share, loss = _excess(tail, total, btail, btotal)
+        return loss, tail, total, calls, t, share
+
+    return _attribution(R, K, top, element)
+
+
+def segment_compact_history_attribution(keys, seg_off, seg_len, K: int, chist, permille: int,
+                                        top: int, cap: int = 0, hist_index=None,
+                                        col_valid=None) -> TailAttribution:
+    """The kernels behind the individual tail score of each row straight from ragged segments of
+    duration keys (``segment_counts``'s addressing) against the rows' own compact history ``chist``
+    (read only), the host twin of ``ops.segment_history_attribution_compact_ragged`` and of
+    ``MatrixReporter.compact_tail_attribution``: ``compact_history_attribution`` over the retained
+    windows' counts."""
+    return compact_history_attribution(segment_counts(keys, seg_off, seg_len, K, cap), chist,
+                                       permille, top, hist_index, col_valid)
 
 
 def quantile_bounds(counts, permille: int):

@@ -925,6 +925,53 @@ def segment_history_attribution_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
     return out
 
 
+def segment_history_attribution_compact_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
+                                               seg_len: Optional[torch.Tensor], K: int,
+                                               max_len: int, chist: torch.Tensor, *, permille: int,
+                                               top: int, cap: int = 0, aligned16: bool = False,
+                                               hist_index: Optional[torch.Tensor] = None,
+                                               hist_stride: int = 0,
+                                               col_valid: Optional[torch.Tensor] = None,
+                                               out: Optional[TailAttribution] = None,
+                                               stream=None) -> TailAttribution:
+    """``segment_history_attribution_ragged`` against a compact history ``chist`` (uint8
+    [R, hist_stride or K, 64], read only; the layout of ``segment_history_scores_compact_ragged``):
+    every output equals, bit for bit, that entry's on the dense expansion of ``chist``
+    (``histograms.compact_to_dense``) -- without the 960 bytes per element.  Between the score and
+    the update call of ``segment_history_scores_compact_ragged`` this sees the history the score
+    saw.  Every other argument and ``out`` as in ``segment_history_attribution_ragged``.  Two
+    launches, no scratch; ``out.loss_all`` is also the workspace."""
+    top, _ = attribution_request(top, "individual")
+    pm = tail_permille(permille)
+    R = _segment_rows(ns, seg_off, seg_len, K)
+    d = ns.device
+    stride = int(hist_stride)
+    if stride < 0 or (stride and hist_index is None and stride < K):
+        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
+    N.require_device(chist, "chist")
+    if chist.dtype != torch.uint8 or chist.data_ptr() % 16:
+        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor")
+    _tail_tensor(chist, "chist", torch.uint8, (R, stride or K, N.CHIST_BYTES))
+    if hist_index is not None:
+        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
+    _u8_vector(col_valid, "col_valid", K)
+    if out is None:
+        out = TailAttribution.empty(R, K, top, d)
+    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
+                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
+                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
+        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
+    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    a = N.SegCHistAttrArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
+                           int(aligned16), top, chist.data_ptr(), stride, N.ptr(hist_index),
+                           N.ptr(col_valid), pm, out.idx.data_ptr(), out.loss.data_ptr(),
+                           out.tail_ns.data_ptr(), out.total_ns.data_ptr(),
+                           out.tail_calls.data_ptr(), out.thr_bucket.data_ptr(),
+                           out.base_share.data_ptr(), out.loss_all.data_ptr())
+    N.call("nvrx_segment_history_attribution_compact_ragged", ctypes.byref(a), _stream(stream))
+    return out
+
+
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,
                scratch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """ref[k] = min_r med[r, k] if every row has k (num > 0), else NaN (reporting.py:255-296)."""
