@@ -34,7 +34,8 @@
  * nvrx_histogram_tail_base / _tail_attribution, nvrx_segment_fleet_histogram_ragged,
  * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged,
  * nvrx_segment_history_scores_ragged, nvrx_segment_history_attribution_ragged,
- * nvrx_segment_history_scores_compact_ragged, nvrx_segment_history_attribution_compact_ragged.
+ * nvrx_segment_history_scores_compact_ragged, nvrx_segment_history_attribution_compact_ragged,
+ * nvrx_compact_history_age, nvrx_histogram_history_age.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -734,6 +735,41 @@ typedef struct nvrx_segchistattr_args {
     double* loss_all;           /* [R][K] */
 } nvrx_segchistattr_args;
 int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args* args, void* stream);
+
+/* Aging the tail histories: every count shifted right by `shift` bits (halved for shift = 1), so
+ * that a history forgets.  No reference counterpart.  Both histories only grow otherwise: counts
+ * add up until they saturate, and a compact element that has used its 12 entries folds every
+ * further bucket downwards.  Aging concerns SLOTS, not columns: every slot of [R][stride] is
+ * aged, and there is no hist_index and no col_valid.
+ *
+ *   nvrx_compact_history_age    chist[R][stride] elements of NVRX_CHIST_BYTES ("Element layout"
+ *     above), in place.  Per element, with s = shift in 1..31:
+ *       count'[i] = count[i] >> s for i < n;
+ *       the entries with count' >= 1 are kept in their order (the buckets stay strictly
+ *       ascending) and moved to the front; n' is their number; entries n'..11 are all zero,
+ *       bucket bytes included.
+ *     Canonical input gives canonical output; an element whose entries are all evicted becomes
+ *     the all-zero (empty) element; an element with n = 0 is not written.  Only the count decides
+ *     whether an entry is used: bucket byte 0 with a count >= 1 is the used bucket 0.
+ *     evicted[r] (u64, [R] or NULL) is the number of entries freed in row r, the sum of n - n';
+ *     full[r] (u64, [R] or NULL) the number of elements of row r with n' = 12 after aging.  Both
+ *     are cleared on the stream first and must not alias each other.
+ *   nvrx_histogram_history_age  the dense u32 hist[R][stride][NVRX_HIST_BINS], in place: every
+ *     word becomes word >> s.  No outputs.
+ * Aging commutes with the dense expansion: the expansion of the aged compact history is the aged
+ * expansion, so the bit-identity between the two histories (while nothing folds) survives aging;
+ * aging by s and then by t is aging by s + t.
+ *
+ * chist / hist 16-byte aligned; evicted and full 8-byte aligned; shift in 1..31; R * stride below
+ * 2^31; for the dense entry also stride * 240 below 2^31 and R * stride * 240 / 4, the 16-byte
+ * vectors of the pass, below 2^31.  R == 0 or stride == 0 launches nothing (outputs untouched).
+ * Stream-ordered: kernels on `stream` only (a clear of the row outputs when one is given, and
+ * the pass), no allocation, no synchronisation, no host read-back, no scratch, no atomics on a
+ * history (the non-zero row sums are added with 64-bit integer atomics, which commute: every run
+ * gives the same result); capturable as a linear chain. */
+int nvrx_compact_history_age(void* chist, int64_t R, int64_t stride, int32_t shift,
+                             uint64_t* evicted, uint64_t* full, void* stream);
+int nvrx_histogram_history_age(uint32_t* hist, int64_t R, int64_t stride, int32_t shift, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

@@ -7,13 +7,15 @@
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
 // histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip,
 // segment_tail_attribution.hip, segment_history.hip, segment_history_attribution.hip,
-// segment_history_compact.hip, segment_history_compact_attribution.hip and records.hip.
+// segment_history_compact.hip, segment_history_compact_attribution.hip, history_age.hip and
+// records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <string>
 
 #include "abi_util.h"
+#include "history_age.h"
 
 namespace {
 thread_local std::string g_last_error;
@@ -618,6 +620,40 @@ int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args
     NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
     return hip_status(nvrx::segment_history_attribution_compact_ragged(*a, S(stream)), fn.c_str());
+}
+
+// aging of the tail histories (history_age.hip): slots, not columns
+int nvrx_compact_history_age(void* chist, int64_t R, int64_t stride, int32_t shift,
+                             uint64_t* evicted, uint64_t* full, void* stream) {
+    const std::string fn("nvrx_compact_history_age");
+    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
+    NVRX_CHECK_ARG(stride >= 0, fn + ": negative stride");
+    NVRX_CHECK_ARG(R == 0 || stride <= (((int64_t)1 << 31) - 1) / R,
+                   fn + ": R * stride must be below 2^31");
+    NVRX_CHECK_ARG(shift >= 1 && shift <= 31, fn + ": shift outside [1, 31]");
+    if (R > 0 && stride > 0) NVRX_CHECK_ARG(chist, fn + ": null chist");
+    NVRX_CHECK_ARG(((uintptr_t)chist & 15) == 0, fn + ": chist not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)evicted & 7) == 0, fn + ": evicted not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)full & 7) == 0, fn + ": full not 8-byte aligned");
+    NVRX_CHECK_ARG(!evicted || evicted != full, fn + ": full aliases evicted");
+    return hip_status(nvrx::compact_history_age(chist, R, stride, shift, evicted, full, S(stream)),
+                      fn.c_str());
+}
+
+int nvrx_histogram_history_age(uint32_t* hist, int64_t R, int64_t stride, int32_t shift, void* stream) {
+    const std::string fn("nvrx_histogram_history_age");
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
+    NVRX_CHECK_ARG(stride >= 0, fn + ": negative stride");
+    NVRX_CHECK_ARG(stride <= lim / NVRX_HIST_BINS, fn + ": stride * 240 must be below 2^31");
+    NVRX_CHECK_ARG(R == 0 || stride <= lim / R, fn + ": R * stride must be below 2^31");
+    // the pass indexes 16-byte vectors, 60 per histogram
+    NVRX_CHECK_ARG(R == 0 || stride == 0 || R * stride <= lim / (NVRX_HIST_BINS / 4),
+                   fn + ": R * stride * 240 must be below 2^31 vectors of four words");
+    NVRX_CHECK_ARG(shift >= 1 && shift <= 31, fn + ": shift outside [1, 31]");
+    if (R > 0 && stride > 0) NVRX_CHECK_ARG(hist, fn + ": null hist");
+    NVRX_CHECK_ARG(((uintptr_t)hist & 15) == 0, fn + ": hist not 16-byte aligned");
+    return hip_status(nvrx::histogram_history_age(hist, R, stride, shift, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

@@ -215,6 +215,8 @@ SIGNATURES = {
     "nvrx_segment_history_scores_compact_ragged": (ctypes.c_int, [ctypes.POINTER(SegCHistArgs), P]),
     "nvrx_segment_history_attribution_compact_ragged": (ctypes.c_int,
                                                         [ctypes.POINTER(SegCHistAttrArgs), P]),
+    "nvrx_compact_history_age": (ctypes.c_int, [P, i64, i64, i32, P, P, P]),
+    "nvrx_histogram_history_age": (ctypes.c_int, [P, i64, i64, i32, P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

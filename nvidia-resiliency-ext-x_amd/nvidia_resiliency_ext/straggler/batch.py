@@ -115,7 +115,16 @@ class BatchIndividualTailScores:
     attribution: Optional[BatchTailAttribution] = None  # with attribute > 0
 
 
+@dataclass
+class TailHistoryAging:
+    """MatrixReporter.age_tail_history: what the age pass did to the compact history (both None
+    when the reporter has no compact history or it was not aged)."""
+    evicted: Optional[np.ndarray] = None  # [R] u64 entries freed per rank
+    full: Optional[np.ndarray] = None     # [R] u64 elements per rank that still hold 12 entries
+
+
 ABSORB_MODES = ("healthy", "always", "never")
+HISTORY_KINDS = ("dense", "compact", "both")
 
 
 @dataclass(eq=False)
@@ -192,6 +201,15 @@ class _ReportBuffers:
                            int(err.view(np.int32)[0]))
 
 
+def _half_life(half_life) -> Optional[int]:
+    """``half_life=`` of the individual tail scores: None or an int >= 1; ValueError if not."""
+    if half_life is None:
+        return None
+    if isinstance(half_life, bool) or not isinstance(half_life, (int, np.integer)) or half_life < 1:
+        raise ValueError(f"half_life must be None or an int >= 1, got {half_life!r}")
+    return int(half_life)
+
+
 class MatrixReporter:
     def __init__(self, R: int, K: int, *, cap: int = 8192, relative: bool = True,
                  individual: bool = True, thr_rel: float = 0.75, thr_ind: float = 0.75,
@@ -227,6 +245,8 @@ class MatrixReporter:
         self._htail = None  # individual_tail_scores(): [R][K][240] history and packed outputs, likewise
         self._rtail = None  # tail_scores_records(): bucketing work tensors, fleet histogram, packed outputs
         self._ctail = None  # individual_tail_scores_records(history="compact"): [R][K][64] history, packed outputs
+        # half_life=: absorbing calls per history since its last aging or reset_tail_history
+        self._absorbed = {"dense": 0, "compact": 0}
 
     @property
     def stats(self) -> ops.SegmentStats:
@@ -594,8 +614,8 @@ class MatrixReporter:
 
     def individual_tail_scores(self, counts: torch.Tensor, permille: int = 990,
                                threshold: Optional[float] = None, absorb: str = "healthy",
-                               tail_calls: bool = False,
-                               attribute: int = 0) -> BatchIndividualTailScores:
+                               tail_calls: bool = False, attribute: int = 0,
+                               half_life: Optional[int] = None) -> BatchIndividualTailScores:
         """A tail score per rank against the rank's OWN history, from the histograms
         ``histograms()`` returned for this interval (int32 device tensor [R, K, 240]): the
         individual leg of ``tail_scores``.  It sees what a comparison with the fleet cannot -- a
@@ -624,11 +644,19 @@ class MatrixReporter:
         device-to-host copy.  The order on the device is score, attribution, update, so the
         attribution sees the history the score saw: ``absorb="always"`` then runs a score-only
         launch, the attribution and an update-only launch -- by the definition the same bits as the
-        fused launch.  Beyond the reference."""
+        fused launch.  ``half_life=N`` (an int >= 1) lets the history forget: the reporter counts
+        the calls with ``absorb != "never"`` on the dense history (this method's and
+        ``individual_tail_scores_records``'s alike) since its last aging or ``reset_tail_history``,
+        and a call that finds N of them first halves every count of the history on its stream
+        (``ops.histogram_history_age``, shift 1) and restarts the count: age, score,
+        (attribution), update.  An interval then weighs half as much after N absorbing calls, a
+        quarter after 2 N.  ``None`` (default): no aging and no further launch.  Beyond the
+        reference."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
             raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
+        half_life = _half_life(half_life)
         if self.exchange:
             raise NotImplementedError("MatrixReporter.individual_tail_scores: tail scores across "
                                       "kernel shards (exchange=True) are not supported")
@@ -637,6 +665,7 @@ class MatrixReporter:
             raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
         self._order_after_inflight()
         t = self._history_tail_work()
+        self._age_before("dense", half_life, absorb)
         buf = t["buf"]
         if top:  # the same layout at the head of a longer buffer
             aoff = self._tail_attr_buffers(t, 41 * R)
@@ -674,8 +703,8 @@ class MatrixReporter:
     def individual_tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor,
                                        permille: int = 990, threshold: Optional[float] = None,
                                        absorb: str = "healthy", tail_calls: bool = False,
-                                       attribute: int = 0,
-                                       history: str = "dense") -> BatchIndividualTailScores:
+                                       attribute: int = 0, history: str = "dense",
+                                       half_life: Optional[int] = None) -> BatchIndividualTailScores:
         """The individual tail scores of ``individual_tail_scores`` for the record streams
         ``report_records`` takes (recs [n, 2] int32 {slot, ns}, rec_off [R + 1] int64, device),
         over the windows that report retains (the last ``cap`` records of every rank and kernel)
@@ -708,12 +737,20 @@ class MatrixReporter:
         (``histograms.segment_compact_history_scores`` on the host).  ``attribute`` is not
         taken together with the compact history (NotImplementedError): ask
         ``compact_tail_attribution()`` after this call, which explains it on request.
-        ``history="dense"`` (default) is the path described above, untouched.  Beyond the
-        reference."""
+        ``history="dense"`` (default) is the path described above, untouched.
+        ``half_life=N`` (an int >= 1) as in ``individual_tail_scores``, per history: a call that
+        finds N calls with ``absorb != "never"`` on ITS history since that history's last aging or
+        ``reset_tail_history`` first halves the history's counts on its stream
+        (``ops.histogram_history_age`` / ``ops.compact_history_age``, shift 1, without the row
+        outputs) and restarts the count: age, score, (attribution), update.  In the compact
+        history the entries that reach zero are evicted, so a full element admits new buckets
+        again and ``.folded`` returns to 0.  ``None`` (default): no aging and no further launch.
+        Beyond the reference."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
             raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
+        half_life = _half_life(half_life)
         if history not in ("dense", "compact"):
             raise ValueError(f"history must be 'dense' or 'compact', got {history!r}")
         if self.exchange:
@@ -731,8 +768,9 @@ class MatrixReporter:
         w = self._records_tail_work(n, history)
         if history == "compact":
             return self._individual_tail_scores_records_compact(recs, rec_off, w, pm, threshold,
-                                                                absorb, tail_calls)
+                                                                absorb, tail_calls, half_life)
         t = self._history_tail_work()
+        self._age_before("dense", half_life, absorb)
         buf = t["buf"]
         if top:  # the same layout at the head of a longer buffer
             aoff = self._tail_attr_buffers(t, 41 * R)
@@ -772,7 +810,7 @@ class MatrixReporter:
                                              host[aoff:], R, top, t["loss_all"]) if top else None)
 
     def _individual_tail_scores_records_compact(self, recs, rec_off, w, pm, threshold, absorb,
-                                                tail_calls) -> BatchIndividualTailScores:
+                                                tail_calls, half_life=None) -> BatchIndividualTailScores:
         """``individual_tail_scores_records(history="compact")`` after its checks: the launches of
         the dense path with ``ops.segment_history_scores_compact_ragged`` on the compact history."""
         R, K, d = self.R, self.K, self.device
@@ -783,6 +821,7 @@ class MatrixReporter:
                                                  device=d),
                                calls=None)
         t = self._ctail
+        self._age_before("compact", half_life, absorb)
         buf = t["buf"]
         i64 = buf[:48 * R].view(torch.int64)
         out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
@@ -873,6 +912,59 @@ class MatrixReporter:
             self._htail["hist"].zero_()
         if self._ctail is not None:
             self._ctail["chist"].zero_()
+        self._absorbed = {"dense": 0, "compact": 0}
+
+    def _age_before(self, kind: str, half_life: Optional[int], absorb: str) -> None:
+        """``half_life=`` at the start of a call on history ``kind`` (allocated by now): the age
+        pass on the current stream when ``half_life`` absorbing calls have been counted, then this
+        call's own count."""
+        if half_life is not None and self._absorbed[kind] >= half_life:
+            if kind == "dense":
+                ops.histogram_history_age(self._htail["hist"], 1)
+            else:  # the row outputs stay NULL: the packed buffers keep their layout
+                ops.compact_history_age(self._ctail["chist"], 1, counts=False)
+            self._absorbed[kind] = 0
+        if absorb != "never":
+            self._absorbed[kind] += 1
+
+    def age_tail_history(self, shift: int = 1, history: str = "both") -> TailHistoryAging:
+        """Let the histories of the individual tail scores forget: every count of the dense
+        history (``history="dense"``), of the compact history (``"compact"``) or of whichever of
+        the two the reporter has (``"both"``, default) becomes ``count >> shift`` (``shift`` in
+        1..31; halved for 1), on the device (``ops.histogram_history_age``,
+        ``ops.compact_history_age``; ``histograms.history_age`` / ``compact_age`` on the host).  In
+        the compact history the entries that reach zero are evicted and the elements re-packed, so
+        an element stuck with 12 stale buckets admits new ones again.  Where no element ever
+        folded the two histories stay bit-identical through aging.  It queues behind reports in
+        flight; a history that was never allocated is skipped, not allocated.  Returns
+        ``TailHistoryAging``: for the compact history ``evicted`` / ``full`` (u64 [R]: the entries
+        freed per rank, the elements per rank still holding 12 entries), in one device-to-host
+        copy; both None when no compact history was aged (then nothing synchronizes).  The
+        ``half_life=`` counts of the aged histories restart.  Beyond the reference."""
+        s = ops.age_shift(shift)
+        if history not in HISTORY_KINDS:
+            raise ValueError(f"history must be one of {HISTORY_KINDS}, got {history!r}")
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.age_tail_history: tail scores across kernel "
+                                      "shards (exchange=True) are not supported")
+        dense = self._htail if history in ("dense", "both") else None
+        compact = self._ctail if history in ("compact", "both") else None
+        if dense is None and compact is None:
+            return TailHistoryAging()
+        self._order_after_inflight()
+        if dense is not None:
+            ops.histogram_history_age(dense["hist"], s)
+            self._absorbed["dense"] = 0
+        if compact is None:
+            return TailHistoryAging()
+        R = self.R
+        if compact.get("age") is None:  # [evicted i64 R][full i64 R]
+            compact["age"] = torch.zeros(2 * R, dtype=torch.int64, device=self.device)
+        out = compact["age"]
+        ops.compact_history_age(compact["chist"], s, evicted=out[:R], full=out[R:])
+        self._absorbed["compact"] = 0
+        host = out.cpu().numpy().view(np.uint64)  # the one device-to-host transfer (synchronizes)
+        return TailHistoryAging(host[:R].copy(), host[R:].copy())
 
     def attribute(self, top: int = 8, kind: str = "relative") -> BatchAttribution:
         """Which kernels made each rank's score what it is: per rank the `top` (1..16) kernels

@@ -38,6 +38,9 @@ history (64 bytes per rank and kernel: at most 12 used buckets, further ones fol
 ``compact_history_attribution`` / ``segment_compact_history_attribution`` of the attribution
 against it (``ops.segment_history_attribution_compact_ragged``,
 ``MatrixReporter.compact_tail_attribution``).
+``history_age`` / ``compact_age`` are the host twins of the aging of the two histories (every count
+shifted right, the compact entries that reach zero evicted; ``ops.histogram_history_age``,
+``ops.compact_history_age``, ``MatrixReporter.age_tail_history``, ``half_life=``).
 """
 from __future__ import annotations
 
@@ -497,6 +500,48 @@ def segment_compact_history_scores(keys, seg_off, seg_len, K: int, chist, permil
     ``compact_history_scores`` (its keywords pass through) over the retained windows' counts."""
     return compact_history_scores(segment_counts(keys, seg_off, seg_len, K, cap), chist, permille,
                                   **kwargs)
+
+
+def _age_shift(shift) -> int:
+    if isinstance(shift, bool) or int(shift) != shift or not 1 <= shift <= 31:
+        raise ValueError(f"shift must be an int in [1, 31], got {shift!r}")
+    return int(shift)
+
+
+def history_age(hist, shift: int) -> np.ndarray:
+    """A dense history ([R, S, 240]; int32 is read as u32) aged by ``shift`` (1..31): every count
+    becomes ``count >> shift`` (u32, a new array).  The host twin of
+    ``ops.histogram_history_age``."""
+    s = _age_shift(shift)
+    H = merge(hist)
+    if H.ndim != 3 or H.shape[2] != BINS:
+        raise ValueError(f"hist must have shape [R, S, {BINS}]")
+    return (H >> s).astype(np.uint32)  # int64 holding u32 values: exact
+
+
+def compact_age(chist, shift: int) -> tuple:
+    """A canonical compact history (uint8 [R, S, 64], left unchanged) aged by ``shift`` (1..31):
+    ``(chist', evicted u64 [R], full u64 [R])``.  Every count of every element becomes ``count >>
+    shift``; the entries that reach zero are evicted and the others keep their order at the front
+    of the element, everything behind them zero, so the result is canonical and an element that
+    loses every entry is the empty history.  ``evicted`` counts the entries freed per row,
+    ``full`` the elements per row that still hold 12 entries.  Python integers: the host twin of
+    ``ops.compact_history_age``."""
+    s = _age_shift(shift)
+    c = _chist_array(chist)
+    if not compact_is_canonical(c).all():
+        raise ValueError("compact_age: an element is not canonical")
+    out = c.copy()
+    R, S, _ = c.shape
+    evicted, full = [0] * R, [0] * R
+    for r in range(R):
+        for k in range(S):
+            old = _chist_entries(c[r, k])
+            new = {b: v >> s for b, v in old.items() if v >> s}
+            out[r, k] = _chist_pack(new)
+            evicted[r] += len(old) - len(new)
+            full[r] += len(new) == CHIST_ENTRIES
+    return out, np.asarray(evicted, np.uint64).reshape(R), np.asarray(full, np.uint64).reshape(R)
 
 
 @dataclass

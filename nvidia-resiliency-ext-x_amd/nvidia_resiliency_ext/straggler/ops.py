@@ -697,6 +697,58 @@ def segment_history_scores_compact_ragged(ns: torch.Tensor, seg_off: torch.Tenso
                              out.base_total_ns, out.strag, calls), folded
 
 
+def age_shift(shift) -> int:
+    """The shift of the aging calls: an int in [1, 31]; ValueError if not."""
+    if isinstance(shift, bool) or not isinstance(shift, numbers.Integral) or not 1 <= shift <= 31:
+        raise ValueError(f"shift must be an int in [1, 31], got {shift!r}")
+    return int(shift)
+
+
+def compact_history_age(chist: torch.Tensor, shift: int = 1, evicted: Optional[torch.Tensor] = None,
+                        full: Optional[torch.Tensor] = None, counts: bool = True, stream=None):
+    """Age a compact history ``chist`` (uint8 [R, S, 64], changed in place): every count of every
+    slot becomes ``count >> shift`` (halved for ``shift`` = 1), the entries that reach zero are
+    evicted, and the element is re-packed to canonical form -- the kept entries in their order at
+    the front, everything behind them zero -- so that the freed entries can admit new buckets.  An
+    element that loses every entry is the empty history again; an empty element is not written.
+    Returns ``(evicted, full)``, int64 [R] device tensors (u64 on the device, cleared first, or the
+    tensors given): the entries freed per row and the elements per row that still hold 12 entries
+    afterwards.  ``counts=False`` passes NULL for both and returns ``(None, None)``.  The dense
+    expansion of the result is ``histogram_history_age`` of the expansion
+    (``histograms.compact_age`` on the host)."""
+    s = age_shift(shift)
+    N.require_device(chist, "chist")
+    if (chist.dtype != torch.uint8 or chist.dim() != 3 or chist.shape[2] != N.CHIST_BYTES or
+            not chist.is_contiguous() or chist.data_ptr() % 16):
+        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor of shape [R, S, 64]")
+    R, S = chist.shape[0], chist.shape[1]
+    if counts:
+        if evicted is None:
+            evicted = torch.empty(R, dtype=torch.int64, device=chist.device)
+        if full is None:
+            full = torch.empty(R, dtype=torch.int64, device=chist.device)
+        _tail_tensor(evicted, "evicted", torch.int64, (R,))
+        _tail_tensor(full, "full", torch.int64, (R,))
+    elif evicted is not None or full is not None:
+        raise ValueError("compact_history_age: evicted / full given with counts=False")
+    N.call("nvrx_compact_history_age", chist.data_ptr(), R, S, s, N.ptr(evicted), N.ptr(full),
+           _stream(stream))
+    return evicted, full
+
+
+def histogram_history_age(hist: torch.Tensor, shift: int = 1, stream=None) -> torch.Tensor:
+    """Age a dense history ``hist`` (int32 [R, S, 240] holding u32 counts, changed in place and
+    returned): every word becomes ``word >> shift`` (``histograms.history_age`` on the host)."""
+    s = age_shift(shift)
+    N.require_device(hist, "hist")
+    if (hist.dtype not in (torch.int32, torch.uint32) or hist.dim() != 3 or
+            hist.shape[2] != N.HIST_BINS or not hist.is_contiguous() or hist.data_ptr() % 16):
+        raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor of shape [R, S, 240]")
+    N.call("nvrx_histogram_history_age", hist.data_ptr(), hist.shape[0], hist.shape[1], s,
+           _stream(stream))
+    return hist
+
+
 def histogram_tail_base(fleet: torch.Tensor, thr: torch.Tensor, out: Optional[torch.Tensor] = None,
                         stream=None) -> torch.Tensor:
     """Per kernel of a fleet histogram (int64 [K, 240]) its weighted {tail, total} ns over the

@@ -412,6 +412,21 @@ class Detector:
         cls._tail_history = _TailHistory()
 
     @classmethod
+    def age_tail_history(cls, shift: int = 1) -> None:
+        """Let the history of ``kernel_individual_tail_score`` forget: every count of every
+        kernel's summed histogram becomes ``count >> shift`` (``shift`` in 1..31; halved for 1), on
+        the device (``ops.histogram_history_age``).  A workload that changed for good -- a new
+        sequence length, a kernel one bucket slower after a driver update -- then stops being
+        scored against a past that no longer exists after a few calls, without the
+        ``reset_tail_history`` that forgets everything at once.  ``IndividualTailScore.intervals``
+        keeps counting the intervals absorbed.  Nothing happens before the first interval.  NOT a
+        collective: local to the rank.  Beyond the reference."""
+        s = ops.age_shift(shift)
+        hist = cls._tail_history.hist
+        if hist is not None and hist.numel():
+            ops.histogram_history_age(hist, s)
+
+    @classmethod
     def kernel_attribution(cls, top: int = 8, kind: str = "relative"):
         """The kernels behind this rank's GPU score in the LAST report: a list of at most `top`
         (1..16) ``KernelAttribution(name, score, loss_us, share)``, largest loss first, where
