@@ -35,7 +35,8 @@
  * nvrx_segment_tail_scores_ragged, nvrx_segment_tail_attribution_ragged,
  * nvrx_segment_history_scores_ragged, nvrx_segment_history_attribution_ragged,
  * nvrx_segment_history_scores_compact_ragged, nvrx_segment_history_attribution_compact_ragged,
- * nvrx_compact_history_age, nvrx_histogram_history_age.
+ * nvrx_compact_history_age, nvrx_histogram_history_age, nvrx_histogram_history_scores_compact,
+ * nvrx_compact_history_from_dense, nvrx_compact_history_to_dense.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -770,6 +771,81 @@ int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args
 int nvrx_compact_history_age(void* chist, int64_t R, int64_t stride, int32_t shift,
                              uint64_t* evicted, uint64_t* full, void* stream);
 int nvrx_histogram_history_age(uint32_t* hist, int64_t R, int64_t stride, int32_t shift, void* stream);
+
+/* The individual tail scores of [R][K][240] counts against the COMPACT history: the fourth corner
+ * of {counts, record streams} x {dense, compact history}.  No reference counterpart.  It adds no
+ * definition; it composes two that stand above.  nvrx_histchist_args has the fields of
+ * nvrx_histtail_args in the same order, with `void* chist` ([R][hist_stride] elements of
+ * NVRX_CHIST_BYTES, "Element layout" above, changed in place) in the place of hist, hist_stride in
+ * elements, and folded at the end.  counts, hist_index, col_valid, skip_rows, permille, mode and
+ * score_thr mean exactly what they do for nvrx_histogram_history_scores.
+ *   SCORE   is nvrx_histogram_history_scores's SCORE with H the dense expansion of the element
+ *           before the call (H[bucket[i]] = count[i] for i < n, zero elsewhere): eligibility
+ *           (col_valid, slot >= 0, N > 0, sum_b C > 0), T, the four u64 sums, tail_calls (0 where
+ *           not eligible), the three separately rounded f64 operations and the strict strag.
+ *   UPDATE  is the compact history's UPDATE ("compact history" above) with c[b] = C[r][k][b]:
+ *           admission of the new buckets in ascending order while entries are free, the target
+ *           t(b) for every other bin, count' = min(count + sum c, 2^32 - 1) with the sum taken in 64
+ *           bits -- every c[b] is a full u32 here and up to 240 of them fold into one entry -- and
+ *           folded[r].  It applies to every (r, k) with col_valid[k], a slot >= 0, skip_rows[r] = 0
+ *           and sum_b C[r][k][b] > 0; an element without samples is not written.
+ *   SCORE | UPDATE scores against the history from before the update.
+ * One history can be continued by this entry and nvrx_segment_history_scores_compact_ragged alike:
+ * on the counts nvrx_segment_histogram_ragged writes for the same segments both leave the same
+ * bytes, folded and outputs.  While nothing folds, the dense expansion and every output equal
+ * nvrx_histogram_history_scores's on the dense history bit for bit.
+ * counts and chist 16-byte aligned; the four u64 outputs, score and folded 8-byte aligned; mode
+ * needs at least one bit; permille in 0..1000; hist_stride 0 or, without hist_index, at least K;
+ * K * 240 and R * K below 2^31.  folded is required with UPDATE and must not alias the other
+ * outputs.  Two columns must not share a slot, and counts and chist must not overlap (neither is
+ * checked).  Canonical input is assumed.  R == 0 or K == 0 launches nothing.  Stream-ordered:
+ * kernels on `stream` only (a clear, the pass, with SCORE a finalize), no allocation, no
+ * synchronisation, no host read-back, no scratch, no atomics on the history; capturable as a
+ * linear chain. */
+typedef struct nvrx_histchist_args {
+    int64_t R, K;
+    const uint32_t* counts;     /* [R][K][NVRX_HIST_BINS] */
+    void* chist;                /* [R][hist_stride] elements of NVRX_CHIST_BYTES, in place */
+    int64_t hist_stride;        /* in elements; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* [K] or NULL */
+    const uint8_t* skip_rows;   /* [R] or NULL */
+    int32_t permille;
+    int32_t mode;               /* NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE */
+    double score_thr;
+    uint64_t* tail_ns;          /* [R] */
+    uint64_t* total_ns;         /* [R] */
+    uint64_t* base_tail_ns;     /* [R] */
+    uint64_t* base_total_ns;    /* [R] */
+    double* score;              /* [R] */
+    uint8_t* strag;             /* [R] or NULL */
+    uint32_t* tail_calls;       /* [R][K] or NULL */
+    uint64_t* folded;           /* [R]; required with UPDATE */
+} nvrx_histchist_args;
+int nvrx_histogram_history_scores_compact(const nvrx_histchist_args* args, void* stream);
+
+/* Conversion between the dense history hist[R][stride][NVRX_HIST_BINS] (u32) and the compact
+ * history chist[R][stride] elements of NVRX_CHIST_BYTES, slot by slot.  No reference counterpart.
+ *   nvrx_compact_history_from_dense  chist[r][s] = the UPDATE of the empty element with
+ *     c[b] = hist[r][s][b]: the 12 lowest used buckets are kept, every bucket above them folds
+ *     into the 12th (the sum taken in 64 bits, saturating at 2^32 - 1).  folded[r] (u64, [R] or
+ *     NULL; cleared on the stream first) is the number of samples folded in row r.  Every element
+ *     is written in full -- an empty dense element gives the all-zero element -- so the target
+ *     needs no clear.
+ *   nvrx_compact_history_to_dense    hist[r][s] = the dense expansion of chist[r][s]
+ *     (H[bucket[i]] = count[i] for i < n, zero elsewhere).  All 240 bins of every element are
+ *     written, so the target needs no clear.  Canonical input is assumed.
+ * to_dense(from_dense(H)) == H exactly when no element of H uses more than 12 buckets, and
+ * from_dense(to_dense(c)) == c for every canonical c.  The two buffers must not overlap (not
+ * checked).  hist and chist 16-byte aligned; folded 8-byte aligned; stride * 240 and R * stride
+ * below 2^31.  R == 0 or stride == 0 launches nothing (folded untouched).  Stream-ordered: kernels
+ * on `stream` only, no allocation, no synchronisation, no host read-back, no scratch, no atomics
+ * on a history (the non-zero folded sums are added with 64-bit integer atomics, which commute);
+ * capturable as a linear chain. */
+int nvrx_compact_history_from_dense(const uint32_t* hist, void* chist, int64_t R, int64_t stride,
+                                    uint64_t* folded, void* stream);
+int nvrx_compact_history_to_dense(const void* chist, uint32_t* hist, int64_t R, int64_t stride,
+                                  void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

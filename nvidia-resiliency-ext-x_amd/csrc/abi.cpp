@@ -7,8 +7,8 @@
 // kernels of segment_stats.hip, scores.hip, attribution.hip, segment_histogram.hip,
 // histogram_scores.hip, histogram_history.hip, histogram_attribution.hip, segment_tail.hip,
 // segment_tail_attribution.hip, segment_history.hip, segment_history_attribution.hip,
-// segment_history_compact.hip, segment_history_compact_attribution.hip, history_age.hip and
-// records.hip.
+// segment_history_compact.hip, segment_history_compact_attribution.hip, history_age.hip,
+// histogram_history_compact.hip and records.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -654,6 +654,89 @@ int nvrx_histogram_history_age(uint32_t* hist, int64_t R, int64_t stride, int32_
     if (R > 0 && stride > 0) NVRX_CHECK_ARG(hist, fn + ": null hist");
     NVRX_CHECK_ARG(((uintptr_t)hist & 15) == 0, fn + ": hist not 16-byte aligned");
     return hip_status(nvrx::histogram_history_age(hist, R, stride, shift, S(stream)), fn.c_str());
+}
+
+// individual tail scores from counts against the compact history (histogram_history_compact.hip):
+// the checks of nvrx_histogram_history_scores and of nvrx_segment_history_scores_compact_ragged
+int nvrx_histogram_history_scores_compact(const nvrx_histchist_args* a, void* stream) {
+    const std::string fn("nvrx_histogram_history_scores_compact");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
+                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
+    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                   fn + ": hist_stride below K without hist_index");
+    const bool score = a->mode & NVRX_HTAIL_SCORE, update = a->mode & NVRX_HTAIL_UPDATE;
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->counts, fn + ": null counts");
+        NVRX_CHECK_ARG(a->chist, fn + ": null chist");
+        if (score) {
+            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
+            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
+            NVRX_CHECK_ARG(a->score, fn + ": null score");
+        }
+        if (update) {
+            NVRX_CHECK_ARG(a->folded, fn + ": null folded");
+            if (score) {
+                const void* const outs[] = {a->tail_ns, a->total_ns, a->base_tail_ns,
+                                            a->base_total_ns, a->score};
+                for (const void* o : outs)
+                    NVRX_CHECK_ARG(o != (const void*)a->folded, fn + ": folded aliases another output");
+            }
+        }
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0, fn + ": counts not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->chist & 15) == 0, fn + ": chist not 16-byte aligned");
+    if (score) {
+        NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->base_tail_ns & 7) == 0, fn + ": base_tail_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->base_total_ns & 7) == 0,
+                       fn + ": base_total_ns not 8-byte aligned");
+        NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
+    }
+    if (update) NVRX_CHECK_ARG(((uintptr_t)a->folded & 7) == 0, fn + ": folded not 8-byte aligned");
+    nvrx_histchist_args b = *a;
+    if (!score) b.tail_calls = nullptr;  // ignored without SCORE
+    if (!update) b.folded = nullptr;     // not written without UPDATE
+    return hip_status(nvrx::histogram_history_scores_compact(b, S(stream)), fn.c_str());
+}
+
+// the conversion between the two histories (histogram_history_compact.hip): slots, not columns
+static int check_convert(const std::string& fn, const void* hist, const void* chist, int64_t R,
+                         int64_t stride) {
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
+    NVRX_CHECK_ARG(stride >= 0, fn + ": negative stride");
+    NVRX_CHECK_ARG(stride <= lim / NVRX_HIST_BINS, fn + ": stride * 240 must be below 2^31");
+    NVRX_CHECK_ARG(R == 0 || stride <= lim / R, fn + ": R * stride must be below 2^31");
+    if (R > 0 && stride > 0) {
+        NVRX_CHECK_ARG(hist, fn + ": null hist");
+        NVRX_CHECK_ARG(chist, fn + ": null chist");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)hist & 15) == 0, fn + ": hist not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)chist & 15) == 0, fn + ": chist not 16-byte aligned");
+    return NVRX_OK;
+}
+
+int nvrx_compact_history_from_dense(const uint32_t* hist, void* chist, int64_t R, int64_t stride,
+                                    uint64_t* folded, void* stream) {
+    const std::string fn("nvrx_compact_history_from_dense");
+    if (int rc = check_convert(fn, hist, chist, R, stride)) return rc;
+    NVRX_CHECK_ARG(((uintptr_t)folded & 7) == 0, fn + ": folded not 8-byte aligned");
+    return hip_status(nvrx::compact_history_from_dense(hist, chist, R, stride, folded, S(stream)),
+                      fn.c_str());
+}
+
+int nvrx_compact_history_to_dense(const void* chist, uint32_t* hist, int64_t R, int64_t stride,
+                                  void* stream) {
+    const std::string fn("nvrx_compact_history_to_dense");
+    if (int rc = check_convert(fn, hist, chist, R, stride)) return rc;
+    return hip_status(nvrx::compact_history_to_dense(chist, hist, R, stride, S(stream)), fn.c_str());
 }
 
 // ------------------------------------------------------------------ scoring

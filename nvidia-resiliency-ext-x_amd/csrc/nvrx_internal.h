@@ -70,6 +70,13 @@ hipError_t segment_history_scores_compact_ragged(const nvrx_segchist_args& a, hi
 // the individual tail score attribution against that compact history
 // (segment_history_compact_attribution.hip)
 hipError_t segment_history_attribution_compact_ragged(const nvrx_segchistattr_args& a, hipStream_t st);
+// individual tail scores from [R][K][240] counts against the compact history, and the conversion
+// between the dense and the compact history (histogram_history_compact.hip)
+hipError_t histogram_history_scores_compact(const nvrx_histchist_args& a, hipStream_t st);
+hipError_t compact_history_from_dense(const uint32_t* hist, void* chist, int64_t R, int64_t stride,
+                                      uint64_t* folded, hipStream_t st);
+hipError_t compact_history_to_dense(const void* chist, uint32_t* hist, int64_t R, int64_t stride,
+                                    hipStream_t st);
 
 hipError_t encode_ns_u32(uint32_t* ns, int64_t n, hipStream_t st);
 

@@ -36,11 +36,12 @@
 //                      64-bit device atomics (cleared by a kernel on the stream first).  Integer
 //                      adds are exact in any order: the result is the same on every run.
 //   segchist_finalize  the three separately rounded f64 operations and strag, as seghist_finalize.
-// bucket_of, sat_add, count_wave, the clear and the finalize restate what segment_history.hip
-// holds in its anonymous namespace; no existing file changes.  Every loop is bounded by K, by the
+// bucket_of, count_wave, the clear and the finalize restate what segment_history.hip holds in its
+// anonymous namespace; the element's load and decode, sat_add and lds_order live in chist_wave.h,
+// shared with histogram_history_compact.hip.  Every loop is bounded by K, by the
 // retained length or by 12.  No kernel uses scratch memory (make asm).
 
-#include "histogram_wave.h"
+#include "chist_wave.h"
 #include "segment_addr.h"
 
 namespace nvrx {
@@ -53,8 +54,8 @@ constexpr int SC_TRIP = SC_WAVES * SC_UNROLL;    // elements per workgroup trip:
 constexpr int SC_TARGET_WGS = 2048;              // 256 CUs x 8 workgroups
 constexpr int SC_LOADS = 4;                      // sample loads in flight per lane
 constexpr int SC_HW = 256;                       // LDS words per wave: 240 bins + the element built
-constexpr int SC_E = NVRX_CHIST_ENTRIES;
-constexpr int SC_WORDS = NVRX_CHIST_BYTES / 4;   // 16: one DPP row
+constexpr int SC_E = CH_E;
+constexpr int SC_WORDS = CH_WORDS;               // 16: one DPP row
 constexpr unsigned SC_NONE = HB;                 // the bucket of a lane past the run's end
 static_assert(SC_WORDS == 16 && SC_UNROLL * SC_WORDS == NVRX_WAVE, "an element is one DPP row");
 static_assert(SC_HW == HB + SC_WORDS && SC_HW == 4 * NVRX_WAVE, "one 16-byte vector per lane clears it");
@@ -64,11 +65,6 @@ static_assert(4 * SC_E + SC_E + 4 == NVRX_CHIST_BYTES, "count[12], bucket[12], n
 __device__ __forceinline__ unsigned bucket_of(unsigned x) {
     const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
     return (sh << 3) + (x >> sh);
-}
-
-__device__ __forceinline__ unsigned sat_add(unsigned h, unsigned c) {
-    const unsigned s = h + c;
-    return s < h ? 0xFFFFFFFFu : s;  // min(h + c, 2^32 - 1) of the 64-bit sum
 }
 
 // 64 buckets, one per lane (SC_NONE: no sample), into the wave's bins h
@@ -84,22 +80,6 @@ __device__ __forceinline__ void count_wave(unsigned b, unsigned* h) {
         live &= ~same;
     }
     if ((live >> lane_id()) & 1) atomicAdd(&h[b], 1u);
-}
-
-// the wave's LDS operations before this are done and visible before those after it
-__device__ __forceinline__ void lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// inclusive u64 prefix inside each 16-lane row (row_shr zero-fills at the row's start)
-__device__ __forceinline__ u64 row_incl_scan_u64(u64 v) {
-    v += dpp_u64<0x111>(v);
-    v += dpp_u64<0x112>(v);
-    v += dpp_u64<0x114>(v);
-    v += dpp_u64<0x118>(v);
-    return v;
 }
 
 __global__ __launch_bounds__(256)
@@ -159,11 +139,8 @@ void segchist_kernel(RaggedSegs segs, nvrx_segchist_args a, int64_t kper) {
         const int64_t sl = row == 0 ? slot[0] : row == 1 ? slot[1] : row == 2 ? slot[2] : slot[3];
         const unsigned word = sl >= 0 ? crow[sl * SC_WORDS + j] : 0u;
         // lanes 0..11 of a row: the entry's count and bucket (zero beyond n, by the canonical form)
-        const unsigned bytes = (unsigned)__builtin_amdgcn_ds_bpermute(4 * ((lane & 48) + SC_E + (j >> 2)),
-                                                                      (int)word);
-        const bool entry = j < SC_E;
-        const unsigned cnt = entry ? word : 0u;
-        const unsigned bkt = entry ? (bytes >> (8 * (j & 3))) & 0xFFu : 0u;
+        unsigned cnt, bkt;
+        chist_entry(word, lane, j, cnt, bkt);
         const u64 incl = SCORE ? row_incl_scan_u64((u64)cnt) : 0ull;
         const u64 wsum = (u64)cnt * weight_of((int)bkt);
 #pragma unroll
@@ -184,13 +161,7 @@ void segchist_kernel(RaggedSegs segs, nvrx_segchist_args a, int64_t kper) {
                 const u64 N = rl_u64(incl, 16 * u + 15);  // lanes 12..15 add nothing
                 if (N != 0) {
                     elig = true;
-                    // (pm (N - 1)) / 1000 without the product leaving 64 bits
-                    const u64 d = (N - 1) / 1000ull, mm = (N - 1) % 1000ull;
-                    const u64 rank = (u64)pm * d + ((u64)pm * mm) / 1000ull;
-                    // incl is non-decreasing over the row and incl[11] = N > rank: the entries at
-                    // or below rank are a prefix, and the entry after them has a count
-                    const int L = (int)__popcll(__ballot(mine && incl <= rank));
-                    t = (int)rl(bkt, 16 * u + L);
+                    t = chist_threshold(incl, bkt, mine, u, pm, N);
                     if (mine) {
                         btotal += wsum;
                         btail += (int)bkt > t ? wsum : 0ull;

@@ -122,6 +122,15 @@ class SegCHistArgs(ctypes.Structure):
     ]
 
 
+class HistCHistArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("counts", P), ("chist", P), ("hist_stride", i64),
+        ("hist_index", P), ("col_valid", P), ("skip_rows", P), ("permille", i32), ("mode", i32),
+        ("score_thr", f64), ("tail_ns", P), ("total_ns", P), ("base_tail_ns", P),
+        ("base_total_ns", P), ("score", P), ("strag", P), ("tail_calls", P), ("folded", P),
+    ]
+
+
 class TailAttrArgs(ctypes.Structure):
     _fields_ = [
         ("R", i64), ("K", i64), ("counts", P), ("kind", i32), ("top", i32), ("thr", P),
@@ -217,6 +226,9 @@ SIGNATURES = {
                                                         [ctypes.POINTER(SegCHistAttrArgs), P]),
     "nvrx_compact_history_age": (ctypes.c_int, [P, i64, i64, i32, P, P, P]),
     "nvrx_histogram_history_age": (ctypes.c_int, [P, i64, i64, i32, P]),
+    "nvrx_histogram_history_scores_compact": (ctypes.c_int, [ctypes.POINTER(HistCHistArgs), P]),
+    "nvrx_compact_history_from_dense": (ctypes.c_int, [P, P, i64, i64, P, P]),
+    "nvrx_compact_history_to_dense": (ctypes.c_int, [P, P, i64, i64, P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),

@@ -244,7 +244,7 @@ class MatrixReporter:
         self._tail = None  # tail_scores(): fleet histogram and packed outputs, allocated at first use
         self._htail = None  # individual_tail_scores(): [R][K][240] history and packed outputs, likewise
         self._rtail = None  # tail_scores_records(): bucketing work tensors, fleet histogram, packed outputs
-        self._ctail = None  # individual_tail_scores_records(history="compact"): [R][K][64] history, packed outputs
+        self._ctail = None  # the compact methods (history="compact"): [R][K][64] history, packed outputs
         # half_life=: absorbing calls per history since its last aging or reset_tail_history
         self._absorbed = {"dense": 0, "compact": 0}
 
@@ -615,7 +615,8 @@ class MatrixReporter:
     def individual_tail_scores(self, counts: torch.Tensor, permille: int = 990,
                                threshold: Optional[float] = None, absorb: str = "healthy",
                                tail_calls: bool = False, attribute: int = 0,
-                               half_life: Optional[int] = None) -> BatchIndividualTailScores:
+                               half_life: Optional[int] = None,
+                               history: str = "dense") -> BatchIndividualTailScores:
         """A tail score per rank against the rank's OWN history, from the histograms
         ``histograms()`` returned for this interval (int32 device tensor [R, K, 240]): the
         individual leg of ``tail_scores``.  It sees what a comparison with the fleet cannot -- a
@@ -650,20 +651,40 @@ class MatrixReporter:
         and a call that finds N of them first halves every count of the history on its stream
         (``ops.histogram_history_age``, shift 1) and restarts the count: age, score,
         (attribution), update.  An interval then weighs half as much after N absorbing calls, a
-        quarter after 2 N.  ``None`` (default): no aging and no further launch.  Beyond the
-        reference."""
+        quarter after 2 N.  ``None`` (default): no aging and no further launch.
+        ``history="compact"`` scores against, and folds the interval into, the compact history of
+        64 bytes per (rank, kernel) in place of 960 -- the SAME one
+        ``individual_tail_scores_records(history="compact")`` keeps (``compact_tail_history()``
+        returns it; the two compact methods continue one history as the two dense methods do):
+        ``ops.histogram_history_scores_compact`` with the same ``absorb`` logic, ``half_life``
+        counted on the compact history.  ``.folded`` (u64 [R], in the same device-to-host copy)
+        counts the samples folded in this call; while it stays 0 every result equals
+        ``history="dense"``'s bit for bit (``histograms.compact_history_scores`` on the host).
+        ``attribute`` is not taken together with the compact history (NotImplementedError): no
+        device entry attributes counts against it.  The call does not touch the bucketing work
+        tensors, so a pending ``compact_tail_attribution()`` stays valid.  ``history="dense"``
+        (default) is the path described above, untouched.  ``convert_tail_history`` moves a
+        reporter from one history to the other.  Beyond the reference."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
             raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
         half_life = _half_life(half_life)
+        if history not in ("dense", "compact"):
+            raise ValueError(f"history must be 'dense' or 'compact', got {history!r}")
         if self.exchange:
             raise NotImplementedError("MatrixReporter.individual_tail_scores: tail scores across "
                                       "kernel shards (exchange=True) are not supported")
+        if history == "compact" and top:
+            raise NotImplementedError("MatrixReporter.individual_tail_scores: attribute= is not "
+                                      "available with the compact history")
         R, K, d = self.R, self.K, self.device
         if tuple(counts.shape) != (R, K, histograms.BINS):
             raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
         self._order_after_inflight()
+        if history == "compact":
+            return self._individual_tail_scores_compact(counts, pm, threshold, absorb, tail_calls,
+                                                        half_life)
         t = self._history_tail_work()
         self._age_before("dense", half_life, absorb)
         buf = t["buf"]
@@ -809,18 +830,58 @@ class MatrixReporter:
                                          attribution=BatchTailAttribution.unpack(
                                              host[aoff:], R, top, t["loss_all"]) if top else None)
 
+    def _compact_tail_work(self, clear: bool = True) -> dict:
+        """The compact history and packed outputs of the two compact methods (they continue the
+        one history), allocated at first use; ``clear=False`` leaves the history uninitialised
+        for a caller that overwrites it in full."""
+        if self._ctail is None:
+            R, K, d = self.R, self.K, self.device
+            new = torch.zeros if clear else torch.empty
+            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns][folded i64 R][strag u8 R]
+            self._ctail = dict(buf=torch.zeros(49 * R, dtype=torch.uint8, device=d),
+                               chist=new((R, K, histograms.CHIST_BYTES), dtype=torch.uint8, device=d),
+                               calls=None)
+        return self._ctail
+
+    def _individual_tail_scores_compact(self, counts, pm, threshold, absorb, tail_calls,
+                                        half_life=None) -> BatchIndividualTailScores:
+        """``individual_tail_scores(history="compact")`` after its checks: the launches of the
+        dense path with ``ops.histogram_history_scores_compact`` on the compact history."""
+        R, K, d = self.R, self.K, self.device
+        t = self._compact_tail_work()
+        self._age_before("compact", half_life, absorb)
+        buf = t["buf"]
+        i64 = buf[:48 * R].view(torch.int64)
+        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
+                                    i64[3 * R:4 * R], i64[4 * R:5 * R], buf[48 * R:])
+        folded = i64[5 * R:]
+        if tail_calls and t["calls"] is None:
+            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
+        res, _ = ops.histogram_history_scores_compact(
+            counts, t["chist"], permille=pm, update=absorb == "always", col_valid=self.col_valid,
+            score_thr=self.thr_ind if threshold is None else threshold,
+            tail_calls=t["calls"] if tail_calls else False, out=out, folded=folded)
+        if absorb == "healthy":
+            ops.histogram_history_scores_compact(counts, t["chist"], permille=pm, score=False,
+                                                 col_valid=self.col_valid, skip_rows=out.strag,
+                                                 folded=folded)
+        elif absorb == "never":
+            folded.zero_()  # no update: nothing folded
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        h64 = host[:48 * R].view(np.uint64).reshape(6, R).copy()
+        btail, btotal = h64[3], h64[4]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
+        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
+                                         host[48 * R:].astype(bool), btail, btotal,
+                                         res.tail_calls, folded=h64[5])
+
     def _individual_tail_scores_records_compact(self, recs, rec_off, w, pm, threshold, absorb,
                                                 tail_calls, half_life=None) -> BatchIndividualTailScores:
         """``individual_tail_scores_records(history="compact")`` after its checks: the launches of
         the dense path with ``ops.segment_history_scores_compact_ragged`` on the compact history."""
         R, K, d = self.R, self.K, self.device
-        if self._ctail is None:
-            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns][folded i64 R][strag u8 R]
-            self._ctail = dict(buf=torch.zeros(49 * R, dtype=torch.uint8, device=d),
-                               chist=torch.zeros((R, K, histograms.CHIST_BYTES), dtype=torch.uint8,
-                                                 device=d),
-                               calls=None)
-        t = self._ctail
+        t = self._compact_tail_work()
         self._age_before("compact", half_life, absorb)
         buf = t["buf"]
         i64 = buf[:48 * R].view(torch.int64)
@@ -902,6 +963,49 @@ class MatrixReporter:
             col_valid=self.col_valid, out=ops.TailAttribution.packed(buf, R, top, t["loss_all"]))
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
         return BatchTailAttribution.unpack(host, R, top, t["loss_all"])
+
+    def convert_tail_history(self, to: str) -> Optional[np.ndarray]:
+        """Move the reporter from one history of the individual tail scores to the other, on the
+        device: ``to="compact"`` converts the dense history into the compact one
+        (``ops.compact_history_from_dense``: per element the 12 lowest used buckets, the rest
+        folded into the 12th), ``to="dense"`` expands the compact history
+        (``ops.compact_history_to_dense``).  The target is allocated if needed and overwritten in
+        full; the source is released, so its memory (960 bytes per rank and kernel for the dense
+        history) goes back to the allocator, and the source's ``half_life=`` count moves to the
+        target.  The calls that follow continue with ``history=to``.  It queues behind reports in
+        flight.  Returns for ``"compact"`` the samples folded per rank (u64 [R], one
+        device-to-host copy; all zero when no element used more than 12 buckets, and then the
+        scores that follow equal the dense history's bit for bit), for ``"dense"`` None (nothing
+        synchronizes).  A pending ``compact_tail_attribution()`` does not survive
+        ``to="dense"``.  RuntimeError if the source history was never allocated.  Beyond the
+        reference."""
+        if to not in ("compact", "dense"):
+            raise ValueError(f"to must be 'compact' or 'dense', got {to!r}")
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.convert_tail_history: tail scores across "
+                                      "kernel shards (exchange=True) are not supported")
+        src = self._htail if to == "compact" else self._ctail
+        if src is None:
+            raise RuntimeError(f"MatrixReporter.convert_tail_history: no "
+                               f"{'dense' if to == 'compact' else 'compact'} history to convert")
+        self._order_after_inflight()
+        if to == "compact":
+            t = self._compact_tail_work(clear=False)
+            folded = t["buf"][40 * self.R:48 * self.R].view(torch.int64)
+            ops.compact_history_from_dense(src["hist"], out=t["chist"], folded=folded)
+            host = folded.cpu().numpy().view(np.uint64).copy()  # the one device-to-host transfer
+            self._htail = None
+            self._absorbed = {"dense": 0, "compact": self._absorbed["dense"]}
+            return host
+        if self._htail is None:  # allocated uninitialised: the conversion writes every bin
+            R, K, d = self.R, self.K, self.device
+            self._htail = dict(buf=torch.zeros(41 * R, dtype=torch.uint8, device=d),
+                               hist=torch.empty((R, K, histograms.BINS), dtype=torch.int32, device=d),
+                               calls=None)
+        ops.compact_history_to_dense(src["chist"], out=self._htail["hist"])
+        self._ctail = None
+        self._absorbed = {"dense": self._absorbed["compact"], "compact": 0}
+        return None
 
     def reset_tail_history(self) -> None:
         """Forget the histories of ``individual_tail_scores`` (dense and compact): the next

@@ -697,6 +697,137 @@ def segment_history_scores_compact_ragged(ns: torch.Tensor, seg_off: torch.Tenso
                              out.base_total_ns, out.strag, calls), folded
 
 
+def histogram_history_scores_compact(counts: torch.Tensor, chist: torch.Tensor, *, permille: int,
+                                     score: bool = True, update: bool = True,
+                                     hist_index: Optional[torch.Tensor] = None, hist_stride: int = 0,
+                                     col_valid: Optional[torch.Tensor] = None,
+                                     skip_rows: Optional[torch.Tensor] = None,
+                                     score_thr: float = 0.75, tail_calls=False,
+                                     out: Optional[HistoryTailScores] = None,
+                                     folded: Optional[torch.Tensor] = None, stream=None):
+    """``histogram_history_scores`` against a compact history ``chist`` (uint8
+    [R, hist_stride or K, 64], changed in place; the format of
+    ``segment_history_scores_compact_ragged``, so one history can be continued by either): the
+    score of ``counts`` ([R, K, 240]) is the dense entry's against every element's dense
+    expansion; ``update`` admits the interval's new buckets in ascending order while the element
+    has free entries and folds every other count into the nearest kept bucket at or below it, the
+    sums taken in 64 bits and saturating.  An element whose counts are all zero is neither scored
+    nor written.  Returns ``(HistoryTailScores, folded)``: ``folded`` (int64 [R], u64 on the
+    device; None without ``update``) counts the folded samples per row -- while it stays 0 the
+    history expands (``compact_history_to_dense``) to exactly the dense entry's and every output
+    equals that entry's bit for bit.  ``counts`` must not overlap ``chist``.  Every other argument
+    and ``out`` as in ``histogram_history_scores``; ``histograms.compact_history_scores`` is the
+    host twin."""
+    pm = tail_permille(permille)
+    if not (score or update):
+        raise ValueError("histogram_history_scores_compact: at least one of score and update")
+    R, K = _tail_counts(counts)
+    d = counts.device
+    stride = int(hist_stride)
+    if stride < 0 or (stride and hist_index is None and stride < K):
+        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
+    N.require_device(chist, "chist")
+    if chist.dtype != torch.uint8 or chist.data_ptr() % 16:
+        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor")
+    _tail_tensor(chist, "chist", torch.uint8, (R, stride or K, N.CHIST_BYTES))
+    if hist_index is not None:
+        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
+    _u8_vector(col_valid, "col_valid", K)
+    _u8_vector(skip_rows, "skip_rows", R)
+    calls = None
+    if score:
+        if out is None:
+            out = HistoryTailScores.empty(R, d)
+        _tail_tensor(out.score, "out.score", torch.float64, (R,))
+        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
+            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
+        if out.strag is not None:
+            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
+        if tail_calls is True:
+            calls = out.tail_calls
+            if calls is None:
+                calls = torch.empty((R, K), dtype=torch.int32, device=d)
+        elif tail_calls is not False and tail_calls is not None:
+            calls = tail_calls
+        if calls is not None:
+            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
+    elif out is None:
+        out = HistoryTailScores()
+    if update:
+        if folded is None:
+            folded = torch.empty(R, dtype=torch.int64, device=d)
+        _tail_tensor(folded, "folded", torch.int64, (R,))
+    else:
+        folded = None
+    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    a = N.HistCHistArgs(R, K, counts.data_ptr(), chist.data_ptr(), stride, N.ptr(hist_index),
+                        N.ptr(col_valid), N.ptr(skip_rows), pm, mode, float(score_thr),
+                        N.ptr(out.tail_ns), N.ptr(out.total_ns), N.ptr(out.base_tail_ns),
+                        N.ptr(out.base_total_ns), N.ptr(out.score), N.ptr(out.strag), N.ptr(calls),
+                        N.ptr(folded))
+    N.call("nvrx_histogram_history_scores_compact", ctypes.byref(a), _stream(stream))
+    return HistoryTailScores(out.score, out.tail_ns, out.total_ns, out.base_tail_ns,
+                             out.base_total_ns, out.strag, calls), folded
+
+
+def _dense_history(hist, name="hist"):
+    N.require_device(hist, name)
+    if (hist.dtype not in (torch.int32, torch.uint32) or hist.dim() != 3 or
+            hist.shape[2] != N.HIST_BINS or not hist.is_contiguous() or hist.data_ptr() % 16):
+        raise ValueError(f"{name} must be a contiguous, 16-byte aligned int32 tensor of shape [R, S, 240]")
+    return hist.shape[0], hist.shape[1]
+
+
+def _compact_history(chist, name="chist"):
+    N.require_device(chist, name)
+    if (chist.dtype != torch.uint8 or chist.dim() != 3 or chist.shape[2] != N.CHIST_BYTES or
+            not chist.is_contiguous() or chist.data_ptr() % 16):
+        raise ValueError(f"{name} must be a contiguous, 16-byte aligned uint8 tensor of shape [R, S, 64]")
+    return chist.shape[0], chist.shape[1]
+
+
+def compact_history_from_dense(hist: torch.Tensor, out: Optional[torch.Tensor] = None,
+                               folded=None, stream=None):
+    """The compact history (uint8 [R, S, 64], ``out`` or a new tensor) of a dense one ``hist``
+    (int32 [R, S, 240] holding u32 counts, unchanged): per element the 12 lowest used buckets, the
+    counts above them folded into the 12th (64-bit sums, saturating) -- the ``update`` of an empty
+    element with those counts, ``histograms.compact_from_dense`` on the host.  Every element of
+    ``out`` is written in full, so it needs no clear; the two tensors must not overlap (not
+    checked).  Returns ``(out, folded)``: ``folded`` (int64 [R], u64 on the device, cleared on the
+    stream first; a tensor given is used) counts the folded samples per row; ``folded=False``
+    passes NULL and returns None for it."""
+    R, S = _dense_history(hist)
+    if out is None:
+        out = torch.empty((R, S, N.CHIST_BYTES), dtype=torch.uint8, device=hist.device)
+    if _compact_history(out, "out") != (R, S):
+        raise ValueError(f"out must have shape [{R}, {S}, 64]")
+    if folded is False:
+        folded = None
+    else:
+        if folded is None:
+            folded = torch.empty(R, dtype=torch.int64, device=hist.device)
+        _tail_tensor(folded, "folded", torch.int64, (R,))
+    N.call("nvrx_compact_history_from_dense", hist.data_ptr(), out.data_ptr(), R, S, N.ptr(folded),
+           _stream(stream))
+    return out, folded
+
+
+def compact_history_to_dense(chist: torch.Tensor, out: Optional[torch.Tensor] = None,
+                             stream=None) -> torch.Tensor:
+    """The dense expansion (int32 [R, S, 240] holding u32 counts, ``out`` or a new tensor) of a
+    canonical compact history ``chist`` (uint8 [R, S, 64], unchanged): ``H[bucket[i]] = count[i]``
+    for the used entries, zero elsewhere (``histograms.compact_to_dense`` on the host).  All 240
+    bins of every element are written, so ``out`` needs no clear; the two tensors must not overlap
+    (not checked)."""
+    R, S = _compact_history(chist)
+    if out is None:
+        out = torch.empty((R, S, N.HIST_BINS), dtype=torch.int32, device=chist.device)
+    if _dense_history(out, "out") != (R, S):
+        raise ValueError(f"out must have shape [{R}, {S}, 240]")
+    N.call("nvrx_compact_history_to_dense", chist.data_ptr(), out.data_ptr(), R, S, _stream(stream))
+    return out
+
+
 def age_shift(shift) -> int:
     """The shift of the aging calls: an int in [1, 31]; ValueError if not."""
     if isinstance(shift, bool) or not isinstance(shift, numbers.Integral) or not 1 <= shift <= 31:
