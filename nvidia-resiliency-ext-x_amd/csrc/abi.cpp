@@ -104,6 +104,101 @@ int check_tail_shape(const char* entry, int64_t R, int64_t K) {
     return NVRX_OK;
 }
 
+// What the tail-score entries share beyond their shape, as templates over the entry's args
+// struct.  Each holds the checks it replaces in their order and with their text; an entry calls
+// them where those checks stood, between the checks that are its own.
+
+// permille and hist_stride of an entry with a history
+template <typename A>
+int check_history_slots(const std::string& fn, const A* a) {
+    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
+    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
+    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
+                   fn + ": hist_stride below K without hist_index");
+    return NVRX_OK;
+}
+// mode, then the above: the request of an individual score
+template <typename A>
+int check_history_request(const std::string& fn, const A* a) {
+    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
+                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
+    return check_history_slots(fn, a);
+}
+// the outputs of an individual score, non-empty shape: the five of SCORE present
+template <typename A>
+int check_history_outputs_set(const std::string& fn, const A* a) {
+    if (!(a->mode & NVRX_HTAIL_SCORE)) return NVRX_OK;
+    NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+    NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+    NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
+    NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
+    NVRX_CHECK_ARG(a->score, fn + ": null score");
+    return NVRX_OK;
+}
+// ... and, against a compact history, UPDATE's folded present and no alias of those five
+template <typename A>
+int check_folded_set(const std::string& fn, const A* a) {
+    if (!(a->mode & NVRX_HTAIL_UPDATE)) return NVRX_OK;
+    NVRX_CHECK_ARG(a->folded, fn + ": null folded");
+    if (a->mode & NVRX_HTAIL_SCORE) {
+        const void* const outs[] = {a->tail_ns, a->total_ns, a->base_tail_ns, a->base_total_ns, a->score};
+        for (const void* o : outs)
+            NVRX_CHECK_ARG(o != (const void*)a->folded, fn + ": folded aliases another output");
+    }
+    return NVRX_OK;
+}
+// the alignment of the five (any shape)
+template <typename A>
+int check_history_outputs_aligned(const std::string& fn, const A* a) {
+    if (!(a->mode & NVRX_HTAIL_SCORE)) return NVRX_OK;
+    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->base_tail_ns & 7) == 0, fn + ": base_tail_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->base_total_ns & 7) == 0, fn + ": base_total_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
+    return NVRX_OK;
+}
+
+// the outputs of a tail attribution: `top` first of all, the eight present for a non-empty shape,
+// the alignment of the five 8-byte ones
+template <typename A>
+int check_attribution_top(const std::string& fn, const A* a) {
+    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
+                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    return NVRX_OK;
+}
+template <typename A>
+int check_attribution_outputs_set(const std::string& fn, const A* a) {
+    NVRX_CHECK_ARG(a->idx, fn + ": null idx");
+    NVRX_CHECK_ARG(a->loss, fn + ": null loss");
+    NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
+    NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
+    NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
+    NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
+    NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
+    NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+    return NVRX_OK;
+}
+template <typename A>
+int check_attribution_outputs_aligned(const std::string& fn, const A* a) {
+    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
+    return NVRX_OK;
+}
+
+// R rows x stride slots of a history on its own (aging, conversion); dense: 240 bins per slot
+int check_slots_shape(const std::string& fn, int64_t R, int64_t stride, bool dense) {
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
+    NVRX_CHECK_ARG(stride >= 0, fn + ": negative stride");
+    if (dense) NVRX_CHECK_ARG(stride <= lim / NVRX_HIST_BINS, fn + ": stride * 240 must be below 2^31");
+    NVRX_CHECK_ARG(R == 0 || stride <= lim / R, fn + ": R * stride must be below 2^31");
+    return NVRX_OK;
+}
+
 bool all_columns(const nvrx_stats_soa* out) {
     return out && out->num && out->min && out->max && out->med && out->avg && out->std;
 }
@@ -305,22 +400,11 @@ int nvrx_histogram_history_scores(const nvrx_histtail_args* a, void* stream) {
     const std::string fn("nvrx_histogram_history_scores");
     NVRX_CHECK_ARG(a, fn + ": null args");
     if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
-    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
-                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
-    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
-    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
-    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
-                   fn + ": hist_stride below K without hist_index");
+    if (int rc = check_history_request(fn, a)) return rc;
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->counts, fn + ": null counts");
         NVRX_CHECK_ARG(a->hist, fn + ": null hist");
-        if (a->mode & NVRX_HTAIL_SCORE) {
-            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
-            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
-            NVRX_CHECK_ARG(a->score, fn + ": null score");
-        }
+        if (int rc = check_history_outputs_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0, fn + ": counts not 16-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
@@ -348,31 +432,20 @@ int nvrx_histogram_tail_base(const uint64_t* fleet, int64_t K, const int32_t* th
 int nvrx_histogram_tail_attribution(const nvrx_tailattr_args* a, void* stream) {
     const std::string fn("nvrx_histogram_tail_attribution");
     NVRX_CHECK_ARG(a, fn + ": null args");
-    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
-                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    if (int rc = check_attribution_top(fn, a)) return rc;
     NVRX_CHECK_ARG(a->kind == NVRX_ATTR_RELATIVE || a->kind == NVRX_ATTR_INDIVIDUAL,
                    fn + ": unknown kind (NVRX_ATTR_RELATIVE or NVRX_ATTR_INDIVIDUAL)");
     if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
     const bool ind = a->kind == NVRX_ATTR_INDIVIDUAL;
     if (ind) {
-        NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
-        NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
-        NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
-                       fn + ": hist_stride below K without hist_index");
+        if (int rc = check_history_slots(fn, a)) return rc;
     }
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->counts, fn + ": null counts");
         NVRX_CHECK_ARG(ind || a->thr, fn + ": the relative kind needs thr");
         NVRX_CHECK_ARG(ind || a->base, fn + ": the relative kind needs base");
         NVRX_CHECK_ARG(!ind || a->hist, fn + ": the individual kind needs hist");
-        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
-        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
-        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
-        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
-        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
-        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+        if (int rc = check_attribution_outputs_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0, fn + ": counts not 16-byte aligned");
     NVRX_CHECK_ARG(!ind || ((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
@@ -428,8 +501,7 @@ int nvrx_segment_tail_scores_ragged(const nvrx_segtail_args* a, void* stream) {
 int nvrx_segment_tail_attribution_ragged(const nvrx_segtailattr_args* a, void* stream) {
     const std::string fn("nvrx_segment_tail_attribution_ragged");
     NVRX_CHECK_ARG(a, fn + ": null args");
-    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
-                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    if (int rc = check_attribution_top(fn, a)) return rc;
     if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
     if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
                               a->max_len, a->cap))
@@ -437,22 +509,11 @@ int nvrx_segment_tail_attribution_ragged(const nvrx_segtailattr_args* a, void* s
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->thr, fn + ": null thr");
         NVRX_CHECK_ARG(a->base, fn + ": null base");
-        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
-        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
-        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
-        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
-        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
-        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+        if (int rc = check_attribution_outputs_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->base & 7) == 0, fn + ": base not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
+    if (int rc = check_attribution_outputs_aligned(fn, a)) return rc;
     return hip_status(nvrx::segment_tail_attribution_ragged(*a, S(stream)), fn.c_str());
 }
 
@@ -464,33 +525,15 @@ int nvrx_segment_history_scores_ragged(const nvrx_seghist_args* a, void* stream)
     if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
                               a->max_len, a->cap))
         return rc;
-    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
-                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
-    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
-    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
-    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
-                   fn + ": hist_stride below K without hist_index");
+    if (int rc = check_history_request(fn, a)) return rc;
     const bool score = a->mode & NVRX_HTAIL_SCORE;
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->hist, fn + ": null hist");
-        if (score) {
-            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
-            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
-            NVRX_CHECK_ARG(a->score, fn + ": null score");
-        }
+        if (int rc = check_history_outputs_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
-    if (score) {
-        NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->base_tail_ns & 7) == 0, fn + ": base_tail_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->base_total_ns & 7) == 0,
-                       fn + ": base_total_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
-    }
+    if (int rc = check_history_outputs_aligned(fn, a)) return rc;
     nvrx_seghist_args b = *a;
     if (!score) b.tail_calls = nullptr;  // ignored without SCORE
     return hip_status(nvrx::segment_history_scores_ragged(b, S(stream)), fn.c_str());
@@ -504,42 +547,16 @@ int nvrx_segment_history_scores_compact_ragged(const nvrx_segchist_args* a, void
     if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
                               a->max_len, a->cap))
         return rc;
-    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
-                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
-    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
-    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
-    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
-                   fn + ": hist_stride below K without hist_index");
+    if (int rc = check_history_request(fn, a)) return rc;
     const bool score = a->mode & NVRX_HTAIL_SCORE, update = a->mode & NVRX_HTAIL_UPDATE;
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->chist, fn + ": null chist");
-        if (score) {
-            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
-            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
-            NVRX_CHECK_ARG(a->score, fn + ": null score");
-        }
-        if (update) {
-            NVRX_CHECK_ARG(a->folded, fn + ": null folded");
-            if (score) {
-                const void* const outs[] = {a->tail_ns, a->total_ns, a->base_tail_ns,
-                                            a->base_total_ns, a->score};
-                for (const void* o : outs)
-                    NVRX_CHECK_ARG(o != (const void*)a->folded, fn + ": folded aliases another output");
-            }
-        }
+        if (int rc = check_history_outputs_set(fn, a)) return rc;
+        if (int rc = check_folded_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->chist & 15) == 0, fn + ": chist not 16-byte aligned");
-    if (score) {
-        NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->base_tail_ns & 7) == 0, fn + ": base_tail_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->base_total_ns & 7) == 0,
-                       fn + ": base_total_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
-    }
+    if (int rc = check_history_outputs_aligned(fn, a)) return rc;
     if (update) NVRX_CHECK_ARG(((uintptr_t)a->folded & 7) == 0, fn + ": folded not 8-byte aligned");
     nvrx_segchist_args b = *a;
     if (!score) b.tail_calls = nullptr;  // ignored without SCORE
@@ -552,34 +569,19 @@ int nvrx_segment_history_scores_compact_ragged(const nvrx_segchist_args* a, void
 int nvrx_segment_history_attribution_ragged(const nvrx_seghistattr_args* a, void* stream) {
     const std::string fn("nvrx_segment_history_attribution_ragged");
     NVRX_CHECK_ARG(a, fn + ": null args");
-    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
-                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    if (int rc = check_attribution_top(fn, a)) return rc;
     if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
     if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
                               a->max_len, a->cap))
         return rc;
-    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
-    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
-    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
-                   fn + ": hist_stride below K without hist_index");
+    if (int rc = check_history_slots(fn, a)) return rc;
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->hist, fn + ": null hist");
-        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
-        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
-        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
-        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
-        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
-        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+        if (int rc = check_attribution_outputs_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->hist & 15) == 0, fn + ": hist not 16-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
+    if (int rc = check_attribution_outputs_aligned(fn, a)) return rc;
     return hip_status(nvrx::segment_history_attribution_ragged(*a, S(stream)), fn.c_str());
 }
 
@@ -588,8 +590,7 @@ int nvrx_segment_history_attribution_ragged(const nvrx_seghistattr_args* a, void
 int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args* a, void* stream) {
     const std::string fn("nvrx_segment_history_attribution_compact_ragged");
     NVRX_CHECK_ARG(a, fn + ": null args");
-    NVRX_CHECK_ARG(a->top >= 1 && a->top <= NVRX_MAX_ATTRIBUTION,
-                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    if (int rc = check_attribution_top(fn, a)) return rc;
     NVRX_CHECK_ARG(a->R >= 0, fn + ": negative R");
     NVRX_CHECK_ARG(a->K >= 0, fn + ": negative K");
     NVRX_CHECK_ARG(a->R == 0 || a->K <= (((int64_t)1 << 31) - 1) / a->R,
@@ -597,28 +598,14 @@ int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args
     if (int rc = check_ragged(fn.c_str(), a->ns, a->seg_off, a->R * a->K, (int64_t)1 << 31,
                               a->max_len, a->cap))
         return rc;
-    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
-    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
-    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
-                   fn + ": hist_stride below K without hist_index");
+    if (int rc = check_history_slots(fn, a)) return rc;
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->chist, fn + ": null chist");
-        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
-        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
-        NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-        NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-        NVRX_CHECK_ARG(a->tail_calls, fn + ": null tail_calls");
-        NVRX_CHECK_ARG(a->thr_bucket, fn + ": null thr_bucket");
-        NVRX_CHECK_ARG(a->base_share, fn + ": null base_share");
-        NVRX_CHECK_ARG(a->loss_all, fn + ": null loss_all");
+        if (int rc = check_attribution_outputs_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->seg_off & 7) == 0, fn + ": seg_off not 8-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->chist & 15) == 0, fn + ": chist not 16-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->base_share & 7) == 0, fn + ": base_share not 8-byte aligned");
-    NVRX_CHECK_ARG(((uintptr_t)a->loss_all & 7) == 0, fn + ": loss_all not 8-byte aligned");
+    if (int rc = check_attribution_outputs_aligned(fn, a)) return rc;
     return hip_status(nvrx::segment_history_attribution_compact_ragged(*a, S(stream)), fn.c_str());
 }
 
@@ -626,10 +613,7 @@ int nvrx_segment_history_attribution_compact_ragged(const nvrx_segchistattr_args
 int nvrx_compact_history_age(void* chist, int64_t R, int64_t stride, int32_t shift,
                              uint64_t* evicted, uint64_t* full, void* stream) {
     const std::string fn("nvrx_compact_history_age");
-    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
-    NVRX_CHECK_ARG(stride >= 0, fn + ": negative stride");
-    NVRX_CHECK_ARG(R == 0 || stride <= (((int64_t)1 << 31) - 1) / R,
-                   fn + ": R * stride must be below 2^31");
+    if (int rc = check_slots_shape(fn, R, stride, false)) return rc;
     NVRX_CHECK_ARG(shift >= 1 && shift <= 31, fn + ": shift outside [1, 31]");
     if (R > 0 && stride > 0) NVRX_CHECK_ARG(chist, fn + ": null chist");
     NVRX_CHECK_ARG(((uintptr_t)chist & 15) == 0, fn + ": chist not 16-byte aligned");
@@ -643,10 +627,7 @@ int nvrx_compact_history_age(void* chist, int64_t R, int64_t stride, int32_t shi
 int nvrx_histogram_history_age(uint32_t* hist, int64_t R, int64_t stride, int32_t shift, void* stream) {
     const std::string fn("nvrx_histogram_history_age");
     const int64_t lim = ((int64_t)1 << 31) - 1;
-    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
-    NVRX_CHECK_ARG(stride >= 0, fn + ": negative stride");
-    NVRX_CHECK_ARG(stride <= lim / NVRX_HIST_BINS, fn + ": stride * 240 must be below 2^31");
-    NVRX_CHECK_ARG(R == 0 || stride <= lim / R, fn + ": R * stride must be below 2^31");
+    if (int rc = check_slots_shape(fn, R, stride, true)) return rc;
     // the pass indexes 16-byte vectors, 60 per histogram
     NVRX_CHECK_ARG(R == 0 || stride == 0 || R * stride <= lim / (NVRX_HIST_BINS / 4),
                    fn + ": R * stride * 240 must be below 2^31 vectors of four words");
@@ -662,43 +643,17 @@ int nvrx_histogram_history_scores_compact(const nvrx_histchist_args* a, void* st
     const std::string fn("nvrx_histogram_history_scores_compact");
     NVRX_CHECK_ARG(a, fn + ": null args");
     if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
-    NVRX_CHECK_ARG(a->mode != 0 && !(a->mode & ~(NVRX_HTAIL_SCORE | NVRX_HTAIL_UPDATE)),
-                   fn + ": mode must be NVRX_HTAIL_SCORE, NVRX_HTAIL_UPDATE or both");
-    NVRX_CHECK_ARG(a->permille >= 0 && a->permille <= 1000, fn + ": permille outside [0, 1000]");
-    NVRX_CHECK_ARG(a->hist_stride >= 0, fn + ": negative hist_stride");
-    NVRX_CHECK_ARG(a->hist_stride == 0 || a->hist_index || a->hist_stride >= a->K,
-                   fn + ": hist_stride below K without hist_index");
+    if (int rc = check_history_request(fn, a)) return rc;
     const bool score = a->mode & NVRX_HTAIL_SCORE, update = a->mode & NVRX_HTAIL_UPDATE;
     if (a->R > 0 && a->K > 0) {
         NVRX_CHECK_ARG(a->counts, fn + ": null counts");
         NVRX_CHECK_ARG(a->chist, fn + ": null chist");
-        if (score) {
-            NVRX_CHECK_ARG(a->tail_ns, fn + ": null tail_ns");
-            NVRX_CHECK_ARG(a->total_ns, fn + ": null total_ns");
-            NVRX_CHECK_ARG(a->base_tail_ns, fn + ": null base_tail_ns");
-            NVRX_CHECK_ARG(a->base_total_ns, fn + ": null base_total_ns");
-            NVRX_CHECK_ARG(a->score, fn + ": null score");
-        }
-        if (update) {
-            NVRX_CHECK_ARG(a->folded, fn + ": null folded");
-            if (score) {
-                const void* const outs[] = {a->tail_ns, a->total_ns, a->base_tail_ns,
-                                            a->base_total_ns, a->score};
-                for (const void* o : outs)
-                    NVRX_CHECK_ARG(o != (const void*)a->folded, fn + ": folded aliases another output");
-            }
-        }
+        if (int rc = check_history_outputs_set(fn, a)) return rc;
+        if (int rc = check_folded_set(fn, a)) return rc;
     }
     NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0, fn + ": counts not 16-byte aligned");
     NVRX_CHECK_ARG(((uintptr_t)a->chist & 15) == 0, fn + ": chist not 16-byte aligned");
-    if (score) {
-        NVRX_CHECK_ARG(((uintptr_t)a->tail_ns & 7) == 0, fn + ": tail_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->total_ns & 7) == 0, fn + ": total_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->base_tail_ns & 7) == 0, fn + ": base_tail_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->base_total_ns & 7) == 0,
-                       fn + ": base_total_ns not 8-byte aligned");
-        NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
-    }
+    if (int rc = check_history_outputs_aligned(fn, a)) return rc;
     if (update) NVRX_CHECK_ARG(((uintptr_t)a->folded & 7) == 0, fn + ": folded not 8-byte aligned");
     nvrx_histchist_args b = *a;
     if (!score) b.tail_calls = nullptr;  // ignored without SCORE
@@ -709,11 +664,7 @@ int nvrx_histogram_history_scores_compact(const nvrx_histchist_args* a, void* st
 // the conversion between the two histories (histogram_history_compact.hip): slots, not columns
 static int check_convert(const std::string& fn, const void* hist, const void* chist, int64_t R,
                          int64_t stride) {
-    const int64_t lim = ((int64_t)1 << 31) - 1;
-    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
-    NVRX_CHECK_ARG(stride >= 0, fn + ": negative stride");
-    NVRX_CHECK_ARG(stride <= lim / NVRX_HIST_BINS, fn + ": stride * 240 must be below 2^31");
-    NVRX_CHECK_ARG(R == 0 || stride <= lim / R, fn + ": R * stride must be below 2^31");
+    if (int rc = check_slots_shape(fn, R, stride, true)) return rc;
     if (R > 0 && stride > 0) {
         NVRX_CHECK_ARG(hist, fn + ": null hist");
         NVRX_CHECK_ARG(chist, fn + ": null chist");

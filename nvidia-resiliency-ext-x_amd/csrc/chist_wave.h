@@ -1,6 +1,6 @@
 // chist_wave.h -- what the kernels on the compact history share (segment_history_compact.hip:
 // record streams; histogram_history_compact.hip: [R][K][240] counts and the dense / compact
-// conversion): a wave holds four 64-byte elements, one per DPP row, one dword per lane -- lanes
+// conversion; segment_history_compact_attribution.hip: the row prefix): a wave holds four 64-byte elements, one per DPP row, one dword per lane -- lanes
 // 0..11 of a row a count, 12..14 the bucket bytes, 15 n (include/nvrx_straggler.h, "Element
 // layout").
 #pragma once
@@ -13,11 +13,6 @@ constexpr int CH_E = NVRX_CHIST_ENTRIES;
 constexpr int CH_WORDS = NVRX_CHIST_BYTES / 4;  // 16: one DPP row
 static_assert(CH_WORDS == 16 && 4 * CH_WORDS == NVRX_WAVE, "an element is one DPP row");
 static_assert(4 * CH_E + CH_E + 4 == NVRX_CHIST_BYTES && CH_E % 4 == 0, "count[12], bucket[12], n");
-
-__device__ __forceinline__ unsigned sat_add(unsigned h, unsigned c) {
-    const unsigned s = h + c;
-    return s < h ? 0xFFFFFFFFu : s;  // min(h + c, 2^32 - 1) of the 64-bit sum
-}
 
 // the wave's LDS operations before this are done and visible before those after it
 __device__ __forceinline__ void lds_order() {

@@ -29,8 +29,6 @@
 // caller's dense [R][K] f64 costs 8 B per element against the 960 / 1,920 B read, and is itself a
 // useful output.  Every loop is bounded by K.  No kernel uses scratch memory (make asm).
 
-#include <type_traits>
-
 #include "histogram_wave.h"
 #include "topk_select.h"
 
@@ -75,16 +73,6 @@ void tail_base_kernel(const u64* __restrict__ fleet, int64_t K, const int32_t* _
     if (lane == 0) *(u64x2*)(base + 2 * k) = (u64x2){tail, total};
 }
 
-// a lane's four bins and their weights: constants of the launch
-struct LaneBins {
-    int b0;
-    unsigned w0, w1, w2, w3;
-};
-__device__ __forceinline__ LaneBins lane_bins(int lane) {
-    const int b0 = 4 * lane;
-    return {b0, weight_of(b0), weight_of(b0 + 1), weight_of(b0 + 2), weight_of(b0 + 3)};
-}
-
 // What a wave holds of one (row, kernel) before the arithmetic: q / g the lane's vector of C / H
 // (zeros in lanes 60..63 and where the element has no base), ok whether it has a base at all, and
 // for the relative leg T and the fleet row's sums.  Everything but q and g is wave-uniform.
@@ -103,8 +91,7 @@ __device__ __forceinline__ ElementIn element_inputs(const nvrx_tailattr_args& a,
     e.T = -1;
     e.btail = e.btotal = 0ull;
     if (IND) {
-        int64_t s = a.hist_index ? (int64_t)a.hist_index[k] : k;
-        if (a.col_valid && !a.col_valid[k]) s = -1;
+        const int64_t s = slot_of(a, k);
         e.ok = s >= 0;
         if (e.ok && lane < HV) {
             e.q = __builtin_nontemporal_load(crow + k * HV);
@@ -179,8 +166,7 @@ __device__ __forceinline__ bool tail_element(const ElementIn& e, int pm, const L
     if (FULL)
         o.calls = wave_sum_u32(((t0 ? q.x : 0u) + (t1 ? q.y : 0u)) + ((t2 ? q.z : 0u) + (t3 ? q.w : 0u)));
     o.T = t;
-    o.share = (double)bl / (double)bt;
-    o.loss = (double)o.tail - (double)o.total * o.share;
+    o.loss = excess(o.tail, o.total, bl, bt, o.share);
     return o.loss == o.loss;
 }
 
@@ -218,76 +204,14 @@ __global__ __launch_bounds__(HA_THREADS) void tail_loss_kernel(nvrx_tailattr_arg
 
 template <bool IND, int TOP>
 __global__ __launch_bounds__(256) void tail_select_kernel(nvrx_tailattr_args a) {
-    __shared__ uint64_t best_k[2][4];
-    __shared__ int32_t best_c[2][4];
-    __shared__ int32_t win[NVRX_MAX_ATTRIBUTION];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int64_t r = blockIdx.x;
     const int64_t K = a.K;
     const double* __restrict__ row = a.loss_all + r * K;
-
-    // this thread's candidates, best first; every index below is a compile-time constant
-    uint64_t ck[TOP];
-    int32_t cc[TOP];
-#pragma unroll
-    for (int i = 0; i < TOP; ++i) {
-        ck[i] = 0;
-        cc[i] = NO_COL;
-    }
-    constexpr int SC = 8;  // every load of a batch is issued before any is used
-    // FIRST: the thread's first batch, whose element c finds at most c candidates held
-    auto batch = [&](const int64_t k0, auto first) {
-        constexpr bool FIRST = decltype(first)::value;
-        double v[SC];
-#pragma unroll
-        for (int c = 0; c < SC; ++c) {
-            const int64_t k = k0 + c * 256;
-            v[c] = k < K ? row[k] : __builtin_nan("");
-        }
-#pragma unroll
-        for (int c = 0; c < SC; ++c) {
-            const uint64_t key = v[c] == v[c] ? loss_key(v[c]) : 0ull;  // NaN: not taken
-            const int32_t col = (int32_t)(k0 + c * 256);
-            const int n = FIRST && c + 1 < TOP ? c + 1 : TOP;  // positions from n on are empty
-            if (__builtin_amdgcn_ballot_w64(key > ck[n - 1]) == 0) continue;  // wave-uniform skip
-            NVRX_TOPK_INSERT(TOP, ck, cc, key, col, n);
-        }
-    };
-    batch(tid, std::true_type{});
-    for (int64_t k0 = (int64_t)tid + 256 * SC; k0 < K; k0 += 256 * SC) batch(k0, std::false_type{});
-
-    // `top` rounds of workgroup argmax over the threads' heads
     const int top = a.top < TOP ? a.top : TOP;
-    for (int j = 0; j < top; ++j) {
-        uint64_t k = ck[0];
-        int32_t c = cc[0];
-        wave_best(k, c);
-        const int b = j & 1;
-        if (lane == 0) {
-            best_k[b][wave] = k;
-            best_c[b][wave] = c;
-        }
-        __syncthreads();
-        uint64_t wk = best_k[b][0];
-        int32_t wc = best_c[b][0];
-#pragma unroll
-        for (int v = 1; v < 4; ++v) {
-            const uint64_t ok = best_k[b][v];
-            const int32_t oc = best_c[b][v];
-            const bool take = before(ok, oc, wk, wc);
-            wk = take ? ok : wk;
-            wc = take ? oc : wc;
-        }
-        if (tid == 0) win[j] = wk != 0 ? wc : -1;
-        // the winner pops its head (columns are distinct, so one thread at most holds wc); the
-        // three waves without it skip the shift
-        const bool pop = wk != 0 && cc[0] == wc;
-        if (__builtin_amdgcn_ballot_w64(pop) == 0) continue;
-        NVRX_TOPK_POP(TOP, ck, cc, pop);
-    }
-    __syncthreads();
+    NVRX_TOPK_WINNERS(TOP, row, K, top, win);
 
     // wave v recomputes winners v, v + 4, ... from the inputs and stores their outputs
     const int64_t stride = a.hist_stride ? a.hist_stride : K;
@@ -303,29 +227,16 @@ __global__ __launch_bounds__(256) void tail_select_kernel(nvrx_tailattr_args a) 
             taken = tail_element<IND, true>(e, a.permille, w, t);
         }
         if (lane != 0) continue;
-        const int64_t o = r * a.top + j;
-        const double qnan = __builtin_nan("");
-        a.idx[o] = taken ? col : -1;
-        a.loss[o] = taken ? t.loss : qnan;
-        a.tail_ns[o] = taken ? t.tail : 0ull;
-        a.total_ns[o] = taken ? t.total : 0ull;
-        a.tail_calls[o] = taken ? t.calls : 0u;
-        a.thr_bucket[o] = taken ? t.T : -1;
-        a.base_share[o] = taken ? t.share : qnan;
+        store_winner(a, r * a.top + j, taken, col, t.loss, t.tail, t.total, t.calls, t.T, t.share);
     }
 }
 
 template <bool IND>
 void launch_select(const nvrx_tailattr_args& a, hipStream_t st) {
     const dim3 g((unsigned)a.R), b(256);
-    if (a.top <= 1)
-        hipLaunchKernelGGL((tail_select_kernel<IND, 1>), g, b, 0, st, a);
-    else if (a.top <= 4)
-        hipLaunchKernelGGL((tail_select_kernel<IND, 4>), g, b, 0, st, a);
-    else if (a.top <= 8)
-        hipLaunchKernelGGL((tail_select_kernel<IND, 8>), g, b, 0, st, a);
-    else
-        hipLaunchKernelGGL((tail_select_kernel<IND, 16>), g, b, 0, st, a);
+    dispatch_top(a.top, [&](auto t) {
+        hipLaunchKernelGGL((tail_select_kernel<IND, decltype(t)::value>), g, b, 0, st, a);
+    });
 }
 
 }  // namespace
@@ -343,13 +254,8 @@ hipError_t histogram_tail_attribution(const nvrx_tailattr_args& a, hipStream_t s
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
     if (a.top < 1 || a.top > NVRX_MAX_ATTRIBUTION) return hipErrorInvalidValue;
     if (a.kind != NVRX_ATTR_RELATIVE && a.kind != NVRX_ATTR_INDIVIDUAL) return hipErrorInvalidValue;
-    // the split rule of histogram_history_scores: about HA_TARGET_WGS workgroups over rows x
-    // splits, a split no shorter than one workgroup trip and a whole number of trips
-    int64_t splits = (HA_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + HA_TRIP - 1) / HA_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + HA_TRIP - 1) / HA_TRIP * HA_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= HA_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, HA_TRIP, HA_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     if (a.kind == NVRX_ATTR_INDIVIDUAL) {
         hipLaunchKernelGGL(tail_loss_kernel<true>, grid, dim3(HA_THREADS), 0, st, a, kper);

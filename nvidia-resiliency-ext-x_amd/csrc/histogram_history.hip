@@ -27,7 +27,8 @@
 //                        are added to the row's four u64 outputs with 64-bit device atomics -- the
 //                        outputs are the accumulators, cleared by a kernel on the stream first.
 //                        Integer adds are exact in any order: the result is the same on every run.
-//   history_finalize     per row the three f64 operations of the score and strag.
+//   tail_score_finalize_kernel<nvrx_histtail_args>   per row the three f64 operations of the
+//                        score and strag (histogram_wave.h, as the clear, clear4_kernel).
 // The split of K exists because rows alone do not fill the device: Detector calls this with R = 1.
 // Every loop is bounded by K.  No kernel uses scratch memory (make asm).
 
@@ -41,22 +42,6 @@ constexpr int HH_WAVES = HH_THREADS / 64;
 constexpr int HH_UNROLL = 4;                     // kernels in flight per wave
 constexpr int HH_TRIP = HH_WAVES * HH_UNROLL;    // kernels per workgroup trip: a split's granule
 constexpr int HH_TARGET_WGS = 2048;              // 256 CUs x 8 workgroups
-
-__global__ __launch_bounds__(256)
-void clear4_u64_kernel(u64* a, u64* b, u64* c, u64* d, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        a[i] = 0ull;
-        b[i] = 0ull;
-        c[i] = 0ull;
-        d[i] = 0ull;
-    }
-}
-
-__device__ __forceinline__ unsigned sat_add(unsigned h, unsigned c) {
-    const unsigned s = h + c;
-    return s < h ? 0xFFFFFFFFu : s;  // min(h + c, 2^32 - 1) of the 64-bit sum
-}
 
 // kernels [blockIdx.y * kper, + kper) of row blockIdx.x
 template <bool SCORE, bool UPDATE, bool CALLS>
@@ -169,21 +154,6 @@ __global__ __launch_bounds__(HH_THREADS) void history_kernel(nvrx_histtail_args 
     if (v) atomicAdd((u64*)dst + r, v);
 }
 
-__global__ __launch_bounds__(256) void history_finalize_kernel(nvrx_histtail_args a) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= a.R) return;
-    const u64 tl = a.tail_ns[r], tt = a.total_ns[r], bl = a.base_tail_ns[r], bt = a.base_total_ns[r];
-    double score = __builtin_nan("");
-    if (tt != 0 && bt != 0) {
-        const double share = (double)tl / (double)tt;
-        const double bs = (double)bl / (double)bt;
-        const double den = 1.0 - bs;
-        if (den != 0.0) score = (1.0 - share) / den;
-    }
-    a.score[r] = score;
-    if (a.strag) a.strag[r] = score < a.score_thr;  // NaN compares false
-}
-
 template <bool SCORE, bool UPDATE, bool CALLS>
 void launch_history(const nvrx_histtail_args& a, dim3 grid, int64_t kper, hipStream_t st) {
     hipLaunchKernelGGL((history_kernel<SCORE, UPDATE, CALLS>), grid, dim3(HH_THREADS), 0, st, a, kper);
@@ -195,16 +165,11 @@ void launch_history(const nvrx_histtail_args& a, dim3 grid, int64_t kper, hipStr
 hipError_t histogram_history_scores(const nvrx_histtail_args& a, hipStream_t st) {
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
     const bool score = a.mode & NVRX_HTAIL_SCORE, update = a.mode & NVRX_HTAIL_UPDATE;
-    // the split rule: about HH_TARGET_WGS workgroups over rows x splits, a split no shorter than
-    // one workgroup trip (HH_TRIP kernels) and a whole number of trips
-    int64_t splits = (HH_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + HH_TRIP - 1) / HH_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + HH_TRIP - 1) / HH_TRIP * HH_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= HH_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, HH_TRIP, HH_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     if (score)
-        hipLaunchKernelGGL(clear4_u64_kernel, dim3((unsigned)((a.R + 255) / 256)), dim3(256), 0, st,
+        hipLaunchKernelGGL(clear4_kernel<u64>, dim3((unsigned)((a.R + 255) / 256)), dim3(256), 0, st,
                            (u64*)a.tail_ns, (u64*)a.total_ns, (u64*)a.base_tail_ns,
                            (u64*)a.base_total_ns, a.R);
     if (!score)
@@ -216,8 +181,8 @@ hipError_t histogram_history_scores(const nvrx_histtail_args& a, hipStream_t st)
         a.tail_calls ? launch_history<true, false, true>(a, grid, kper, st)
                      : launch_history<true, false, false>(a, grid, kper, st);
     if (score)
-        hipLaunchKernelGGL(history_finalize_kernel, dim3((unsigned)((a.R + 255) / 256)), dim3(256), 0,
-                           st, a);
+        hipLaunchKernelGGL(tail_score_finalize_kernel<nvrx_histtail_args>, dim3((unsigned)((a.R + 255) / 256)), dim3(256),
+                           0, st, a);
     return hipGetLastError();
 }
 

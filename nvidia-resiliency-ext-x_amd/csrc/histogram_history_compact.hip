@@ -28,7 +28,8 @@
 //                      the non-zero sums added with 64-bit device atomics (cleared by a kernel on
 //                      the stream first).  Integer adds are exact in any order: the result is the
 //                      same on every run.
-//   histchist_finalize the three separately rounded f64 operations and strag, as history_finalize.
+//   tail_score_finalize_kernel<nvrx_histchist_args>   the three separately rounded f64 operations
+//                      and strag (histogram_wave.h, as the clear, clear4_folded_kernel).
 //   from_dense_kernel  chist = UPDATE of the empty element with the dense counts: the merge above
 //                      with no used bucket.  The [R][stride] elements are one flat array; a wave
 //                      owns a contiguous run and has HC_UNROLL loads in flight.  Every element is
@@ -105,19 +106,6 @@ __device__ __forceinline__ unsigned chist_merge(const u32x4 c, unsigned used, co
     if (lane == 0) m->out[CH_WORDS - 1] = n2;
     lds_order();
     return lane < CH_WORDS ? m->out[lane] : 0u;
-}
-
-__global__ __launch_bounds__(256)
-void histchist_clear_kernel(u64* a, u64* b, u64* c, u64* d, u64* folded, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    if (a) {  // SCORE
-        a[i] = 0ull;
-        b[i] = 0ull;
-        c[i] = 0ull;
-        d[i] = 0ull;
-    }
-    if (folded) folded[i] = 0ull;  // UPDATE
 }
 
 // kernels [blockIdx.y * kper, + kper) of row blockIdx.x
@@ -242,21 +230,6 @@ __global__ __launch_bounds__(HC_THREADS) void histchist_kernel(nvrx_histchist_ar
     if (v) atomicAdd((u64*)dst + r, v);
 }
 
-__global__ __launch_bounds__(256) void histchist_finalize_kernel(nvrx_histchist_args a) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= a.R) return;
-    const u64 tl = a.tail_ns[r], tt = a.total_ns[r], bl = a.base_tail_ns[r], bt = a.base_total_ns[r];
-    double score = __builtin_nan("");
-    if (tt != 0 && bt != 0) {
-        const double share = (double)tl / (double)tt;
-        const double bs = (double)bl / (double)bt;
-        const double den = 1.0 - bs;
-        if (den != 0.0) score = (1.0 - share) / den;
-    }
-    a.score[r] = score;
-    if (a.strag) a.strag[r] = score < a.score_thr;  // NaN compares false
-}
-
 template <bool SCORE, bool UPDATE, bool CALLS>
 void launch_histchist(const nvrx_histchist_args& a, dim3 grid, int64_t kper, hipStream_t st) {
     hipLaunchKernelGGL((histchist_kernel<SCORE, UPDATE, CALLS>), grid, dim3(HC_THREADS), 0, st, a, kper);
@@ -355,16 +328,11 @@ void convert_grid(int64_t E, int64_t& per_wave, dim3& grid) {
 hipError_t histogram_history_scores_compact(const nvrx_histchist_args& a, hipStream_t st) {
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
     const bool score = a.mode & NVRX_HTAIL_SCORE, update = a.mode & NVRX_HTAIL_UPDATE;
-    // the split rule of histogram_history.hip: about HC_TARGET_WGS workgroups over rows x splits, a
-    // split no shorter than one workgroup trip (HC_TRIP kernels) and a whole number of trips
-    int64_t splits = (HC_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + HC_TRIP - 1) / HC_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + HC_TRIP - 1) / HC_TRIP * HC_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= HC_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, HC_TRIP, HC_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     const dim3 rows((unsigned)((a.R + 255) / 256));
-    hipLaunchKernelGGL(histchist_clear_kernel, rows, dim3(256), 0, st,
+    hipLaunchKernelGGL(clear4_folded_kernel<u64>, rows, dim3(256), 0, st,
                        score ? (u64*)a.tail_ns : nullptr, (u64*)a.total_ns, (u64*)a.base_tail_ns,
                        (u64*)a.base_total_ns, update ? (u64*)a.folded : nullptr, a.R);
     if (!score)
@@ -375,7 +343,8 @@ hipError_t histogram_history_scores_compact(const nvrx_histchist_args& a, hipStr
     else
         a.tail_calls ? launch_histchist<true, false, true>(a, grid, kper, st)
                      : launch_histchist<true, false, false>(a, grid, kper, st);
-    if (score) hipLaunchKernelGGL(histchist_finalize_kernel, rows, dim3(256), 0, st, a);
+    if (score)
+        hipLaunchKernelGGL(tail_score_finalize_kernel<nvrx_histchist_args>, rows, dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

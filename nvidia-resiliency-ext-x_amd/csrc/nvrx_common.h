@@ -223,6 +223,16 @@ __device__ __forceinline__ float ns_to_us_narrow(unsigned ns) {
     return __builtin_fmaf(__builtin_fmaf(-q, 1000.0f, f), 0.001f, q);
 }
 
+// Host side: the split rule of every kernel whose grid is (rows, splits of K).  About target_wgs
+// workgroups over rows x splits, a split (kper columns) no shorter than one workgroup trip and a
+// whole number of trips.  The result is <= target_wgs: it fits grid.y.  Needs R, K > 0.
+inline int64_t row_splits(int64_t R, int64_t K, int64_t trip, int64_t target_wgs, int64_t* kper) {
+    int64_t splits = (target_wgs + R - 1) / R;
+    splits = splits < (K + trip - 1) / trip ? splits : (K + trip - 1) / trip;
+    *kper = ((K + splits - 1) / splits + trip - 1) / trip * trip;
+    return (K + *kper - 1) / *kper;
+}
+
 }  // namespace nvrx
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

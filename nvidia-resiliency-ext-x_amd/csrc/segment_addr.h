@@ -37,6 +37,29 @@ struct RaggedSegs {  // segment s = base[off[s] : off[s] + len[s]] (len NULL: of
     }
 };
 
+// The sample loads of the tail kernels that sort a wave's 64 ragged segments into two treatments
+// (segment_tail.hip, segment_tail_attribution.hip): a retained run <= ST_LANE_MAX is walked by the
+// lane that holds it, a longer one by the whole wave.
+constexpr int ST_LANE_MAX = 16;  // the longest retained run a lane walks alone
+constexpr int ST_UNROLL = 4;     // loads in flight per lane
+
+__device__ __forceinline__ const uint32_t* rl_ptr(const uint32_t* p, int l) {
+    const uint64_t b = (uint64_t)(uintptr_t)p;
+    return (const uint32_t*)(uintptr_t)(((uint64_t)rl((unsigned)(b >> 32), l) << 32) | rl((unsigned)b, l));
+}
+// samples [base, base + 64 ST_UNROLL) of a segment of m, 64 consecutive ones per load; a lane past
+// the end re-reads the last sample (its slot is then masked by the caller)
+__device__ __forceinline__ void wave_load(const uint32_t* q, int m, int base, unsigned (&x)[ST_UNROLL]) {
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u)
+        x[u] = __builtin_nontemporal_load(q + min(base + u * 64 + lane_id(), m - 1));
+}
+// samples [i, i + ST_UNROLL) of a lane's own segment of n
+__device__ __forceinline__ void lane_load(const uint32_t* p, int n, int i, unsigned (&x)[ST_UNROLL]) {
+#pragma unroll
+    for (int u = 0; u < ST_UNROLL; ++u) x[u] = p[min(i + u, n - 1)];
+}
+
 // need = retained length + offset in the first 16-byte vector: what a wave has to hold
 __device__ __forceinline__ int seg_need(const uint32_t* p, int n) {
     return n + (int)(((uintptr_t)p & 15) >> 2);

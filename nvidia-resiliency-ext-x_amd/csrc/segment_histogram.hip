@@ -40,23 +40,18 @@
 // memset needed), otherwise the counts are added to what is there.  seg_len < 0: untouched;
 // empty: zero bins (nothing added) and num 0.  Segments of a few samples still take a whole wave.
 
+#include "histogram_wave.h"
 #include "segment_wave.h"
 
 namespace nvrx {
 namespace {
 
-constexpr int HB = NVRX_HIST_BINS;
 constexpr int HW = 256;                  // LDS words per wave: 240 bins, the spare bin, padding
 constexpr unsigned SPARE = HB;           // where slots outside the segment count
 constexpr unsigned SPARE2 = HB + 1;      // a bucket no slot ever has
 constexpr int HIST_WAVE_MAX = 16384;     // the longest need (length + offset) of the wave kernel
 constexpr int HIST_REPLACE = 16;         // misses in one register that replace a kept bucket
 static_assert(HB % 4 == 0 && HB + 2 <= HW, "bins");
-
-__device__ __forceinline__ unsigned bucket_of(unsigned x) {
-    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
-    return (sh << 3) + (x >> sh);
-}
 
 // the two buckets a wave keeps in scalar registers, with their counts
 struct Kept {

@@ -34,11 +34,12 @@
 //                      to the row's four u64 outputs with 64-bit device atomics (cleared by a
 //                      kernel on the stream first).  Integer adds are exact in any order: the
 //                      result is the same on every run.
-//   seghist_finalize   per row the three separately rounded f64 operations of the score and strag:
-//                      the operations of history_finalize_kernel.
-// bucket_of, weight_of's use, the clear and the finalize restate what segment_tail.hip and
-// histogram_history.hip hold in their anonymous namespaces; no existing file changes.  Every loop
-// is bounded by K or by the retained length.  No kernel uses scratch memory (make asm).
+//   tail_score_finalize_kernel<nvrx_seghist_args>   per row the three separately rounded f64
+//                      operations of the score and strag (histogram_wave.h, as the clear,
+//                      clear4_kernel).
+// bucket_of, sat_add, count_wave and slot_of are histogram_wave.h's too, the split rule is
+// nvrx_common.h's row_splits.  Every loop is bounded by K or by the retained length.  No kernel
+// uses scratch memory (make asm).
 
 #include "histogram_wave.h"
 #include "segment_addr.h"
@@ -55,43 +56,6 @@ constexpr int SH_LOADS = 4;                      // sample loads in flight per l
 constexpr int SH_HW = 256;                       // LDS words per histogram: 64 lanes x one vector
 constexpr unsigned SH_NONE = HB;                 // the bucket of a lane past the run's end
 static_assert(SH_HW >= HB + 1 && SH_HW == 4 * NVRX_WAVE, "one 16-byte vector per lane clears it");
-
-// segment_histogram.hip's bucket expression: sh = e - 3 for x >= 8, 0 below
-__device__ __forceinline__ unsigned bucket_of(unsigned x) {
-    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
-    return (sh << 3) + (x >> sh);
-}
-
-__device__ __forceinline__ unsigned sat_add(unsigned h, unsigned c) {
-    const unsigned s = h + c;
-    return s < h ? 0xFFFFFFFFu : s;  // min(h + c, 2^32 - 1) of the 64-bit sum
-}
-
-// 64 buckets, one per lane (SH_NONE: no sample), into the wave's bins h
-__device__ __forceinline__ void count_wave(unsigned b, unsigned* h) {
-    uint64_t live = __ballot(b != SH_NONE);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        if (!live) return;  // wave-uniform
-        const int l = __builtin_ctzll(live);
-        const unsigned lead = rl(b, l);
-        const uint64_t same = __ballot(b == lead);
-        if (lane_id() == l) atomicAdd(&h[lead], (unsigned)__popcll(same));
-        live &= ~same;
-    }
-    if ((live >> lane_id()) & 1) atomicAdd(&h[b], 1u);
-}
-
-__global__ __launch_bounds__(256)
-void seghist_clear_kernel(u64* a, u64* b, u64* c, u64* d, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        a[i] = 0ull;
-        b[i] = 0ull;
-        c[i] = 0ull;
-        d[i] = 0ull;
-    }
-}
 
 // kernels [blockIdx.y * kper, + kper) of row blockIdx.x
 template <bool SCORE, bool UPDATE, bool CALLS>
@@ -128,8 +92,7 @@ void seghist_kernel(RaggedSegs segs, nvrx_seghist_args a, int64_t kper) {
             run[u] = nullptr;
             len[u] = 0;
             if (k < ke) {
-                int64_t s = a.hist_index ? (int64_t)a.hist_index[k] : k;
-                if (a.col_valid && !a.col_valid[k]) s = -1;
+                int64_t s = slot_of(a, k);
                 if (s >= 0) segs.get(r * K + k, run[u], len[u]);
                 if (len[u] <= 0) s = -1;  // an empty element: no score, no update, no read of H
                 slot[u] = s;
@@ -205,7 +168,7 @@ void seghist_kernel(RaggedSegs segs, nvrx_seghist_args a, int64_t kper) {
                             tail += hit ? w : 0ull;
                             if (CALLS) calls += (unsigned)__popcll(__ballot(hit));
                         }
-                        if (count) count_wave(live ? b : SH_NONE, hb);
+                        if (count) count_wave<SH_NONE>(live ? b : SH_NONE, hb);
                     }
                 }
             }
@@ -242,21 +205,6 @@ void seghist_kernel(RaggedSegs segs, nvrx_seghist_args a, int64_t kper) {
     if (v) atomicAdd((u64*)dst + r, v);
 }
 
-__global__ __launch_bounds__(256) void seghist_finalize_kernel(nvrx_seghist_args a) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= a.R) return;
-    const u64 tl = a.tail_ns[r], tt = a.total_ns[r], bl = a.base_tail_ns[r], bt = a.base_total_ns[r];
-    double score = __builtin_nan("");
-    if (tt != 0 && bt != 0) {
-        const double share = (double)tl / (double)tt;
-        const double bs = (double)bl / (double)bt;
-        const double den = 1.0 - bs;
-        if (den != 0.0) score = (1.0 - share) / den;
-    }
-    a.score[r] = score;
-    if (a.strag) a.strag[r] = score < a.score_thr;  // NaN compares false
-}
-
 template <bool SCORE, bool UPDATE, bool CALLS>
 void launch_seghist(const nvrx_seghist_args& a, dim3 grid, int64_t kper, hipStream_t st) {
     hipLaunchKernelGGL((seghist_kernel<SCORE, UPDATE, CALLS>), grid, dim3(SH_THREADS), 0, st,
@@ -269,17 +217,12 @@ void launch_seghist(const nvrx_seghist_args& a, dim3 grid, int64_t kper, hipStre
 hipError_t segment_history_scores_ragged(const nvrx_seghist_args& a, hipStream_t st) {
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
     const bool score = a.mode & NVRX_HTAIL_SCORE, update = a.mode & NVRX_HTAIL_UPDATE;
-    // the split rule of histogram_history.hip: about SH_TARGET_WGS workgroups over rows x splits, a
-    // split no shorter than one workgroup trip (SH_TRIP kernels) and a whole number of trips
-    int64_t splits = (SH_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + SH_TRIP - 1) / SH_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + SH_TRIP - 1) / SH_TRIP * SH_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= SH_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, SH_TRIP, SH_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     const dim3 rows((unsigned)((a.R + 255) / 256));
     if (score)
-        hipLaunchKernelGGL(seghist_clear_kernel, rows, dim3(256), 0, st, (u64*)a.tail_ns,
+        hipLaunchKernelGGL(clear4_kernel<u64>, rows, dim3(256), 0, st, (u64*)a.tail_ns,
                            (u64*)a.total_ns, (u64*)a.base_tail_ns, (u64*)a.base_total_ns, a.R);
     if (!score)
         launch_seghist<false, true, false>(a, grid, kper, st);
@@ -289,7 +232,8 @@ hipError_t segment_history_scores_ragged(const nvrx_seghist_args& a, hipStream_t
     else
         a.tail_calls ? launch_seghist<true, false, true>(a, grid, kper, st)
                      : launch_seghist<true, false, false>(a, grid, kper, st);
-    if (score) hipLaunchKernelGGL(seghist_finalize_kernel, rows, dim3(256), 0, st, a);
+    if (score)
+        hipLaunchKernelGGL(tail_score_finalize_kernel<nvrx_seghist_args>, rows, dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -37,12 +37,10 @@
 //          and a population count, and lane 0 stores every per-winner output.  What is stored
 //          comes from the inputs, the key only orders; integer sums do not depend on their order,
 //          so the recomputed loss is the loss that ranked the winner.
-// Every (r, k) has one owner: no atomics, no scratch, no clear.  bucket_of and the masked sample
-// load restate what segment_history.hip holds in its anonymous namespace; no existing file
-// changes.  Every loop is bounded by K or a retained length.  No kernel uses scratch memory (make
-// asm).
-
-#include <type_traits>
+// Every (r, k) has one owner: no atomics, no scratch, no clear.  bucket_of, lane_bins, slot_of and
+// `excess` are histogram_wave.h's; the select's first half (NVRX_TOPK_WINNERS), the winner's
+// stores and the choice of TOP are topk_select.h's.  Every loop is bounded by K or a retained
+// length.  No kernel uses scratch memory (make asm).
 
 #include "histogram_wave.h"
 #include "segment_addr.h"
@@ -57,22 +55,6 @@ constexpr int SHA_UNROLL = 4;                      // elements in flight per wav
 constexpr int SHA_TRIP = SHA_WAVES * SHA_UNROLL;   // elements per workgroup trip: a split's granule
 constexpr int SHA_TARGET_WGS = 2048;               // 256 CUs x 8 workgroups
 constexpr int SHA_LOADS = 4;                       // sample loads in flight per lane
-
-// segment_histogram.hip's bucket expression: sh = e - 3 for x >= 8, 0 below
-__device__ __forceinline__ unsigned bucket_of(unsigned x) {
-    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
-    return (sh << 3) + (x >> sh);
-}
-
-// a lane's four bins and their weights: constants of the launch
-struct LaneBins {
-    int b0;
-    unsigned w0, w1, w2, w3;
-};
-__device__ __forceinline__ LaneBins lane_bins(int lane) {
-    const int b0 = 4 * lane;
-    return {b0, weight_of(b0), weight_of(b0 + 1), weight_of(b0 + 2), weight_of(b0 + 3)};
-}
 
 // One element before its wave reductions: the lane's part of the four sums; T, the calls and
 // whether the history holds a sample at all (N > 0) are wave-uniform.
@@ -135,20 +117,6 @@ __device__ __forceinline__ Partial element_partials(const u32x4 g, const uint32_
     return p;
 }
 
-// the three f64 operations of the definition, each rounded separately (-ffp-contract=off): both
-// kernels call it, so a winner's stored loss is the loss that ranked it
-__device__ __forceinline__ double excess(u64 tail, u64 total, u64 btail, u64 btotal, double& share) {
-    share = (double)btail / (double)btotal;
-    return (double)tail - (double)total * share;
-}
-
-// slot of column k (wave-uniform), -1 where the column is not eligible
-__device__ __forceinline__ int64_t slot_of(const nvrx_seghistattr_args& a, int64_t k) {
-    int64_t s = a.hist_index ? (int64_t)a.hist_index[k] : k;
-    if (a.col_valid && !a.col_valid[k]) s = -1;
-    return s;
-}
-
 // kernels [blockIdx.y * kper, + kper) of row blockIdx.x
 __global__ __launch_bounds__(SHA_THREADS)
 void seghist_loss_kernel(RaggedSegs segs, nvrx_seghistattr_args a, int64_t kper) {
@@ -207,76 +175,14 @@ void seghist_loss_kernel(RaggedSegs segs, nvrx_seghistattr_args a, int64_t kper)
 template <int TOP>
 __global__ __launch_bounds__(256)
 void seghist_select_kernel(RaggedSegs segs, nvrx_seghistattr_args a) {
-    __shared__ uint64_t best_k[2][4];
-    __shared__ int32_t best_c[2][4];
-    __shared__ int32_t win[NVRX_MAX_ATTRIBUTION];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int64_t r = blockIdx.x;
     const int64_t K = a.K;
     const double* __restrict__ row = a.loss_all + r * K;
-
-    // this thread's candidates, best first; every index below is a compile-time constant
-    uint64_t ck[TOP];
-    int32_t cc[TOP];
-#pragma unroll
-    for (int i = 0; i < TOP; ++i) {
-        ck[i] = 0;
-        cc[i] = NO_COL;
-    }
-    constexpr int SC = 8;  // every load of a batch is issued before any is used
-    // FIRST: the thread's first batch, whose element c finds at most c candidates held
-    auto batch = [&](const int64_t k0, auto first) {
-        constexpr bool FIRST = decltype(first)::value;
-        double v[SC];
-#pragma unroll
-        for (int c = 0; c < SC; ++c) {
-            const int64_t k = k0 + c * 256;
-            v[c] = k < K ? row[k] : __builtin_nan("");
-        }
-#pragma unroll
-        for (int c = 0; c < SC; ++c) {
-            const uint64_t key = v[c] == v[c] ? loss_key(v[c]) : 0ull;  // NaN: not taken
-            const int32_t col = (int32_t)(k0 + c * 256);
-            const int n = FIRST && c + 1 < TOP ? c + 1 : TOP;  // positions from n on are empty
-            if (__builtin_amdgcn_ballot_w64(key > ck[n - 1]) == 0) continue;  // wave-uniform skip
-            NVRX_TOPK_INSERT(TOP, ck, cc, key, col, n);
-        }
-    };
-    batch(tid, std::true_type{});
-    for (int64_t k0 = (int64_t)tid + 256 * SC; k0 < K; k0 += 256 * SC) batch(k0, std::false_type{});
-
-    // `top` rounds of workgroup argmax over the threads' heads
     const int top = a.top < TOP ? a.top : TOP;
-    for (int j = 0; j < top; ++j) {
-        uint64_t k = ck[0];
-        int32_t c = cc[0];
-        wave_best(k, c);
-        const int b = j & 1;
-        if (lane == 0) {
-            best_k[b][wave] = k;
-            best_c[b][wave] = c;
-        }
-        __syncthreads();
-        uint64_t wk = best_k[b][0];
-        int32_t wc = best_c[b][0];
-#pragma unroll
-        for (int v = 1; v < 4; ++v) {
-            const uint64_t ok = best_k[b][v];
-            const int32_t oc = best_c[b][v];
-            const bool take = before(ok, oc, wk, wc);
-            wk = take ? ok : wk;
-            wc = take ? oc : wc;
-        }
-        if (tid == 0) win[j] = wk != 0 ? wc : -1;
-        // the winner pops its head (columns are distinct, so one thread at most holds wc); the
-        // three waves without it skip the shift
-        const bool pop = wk != 0 && cc[0] == wc;
-        if (__builtin_amdgcn_ballot_w64(pop) == 0) continue;
-        NVRX_TOPK_POP(TOP, ck, cc, pop);
-    }
-    __syncthreads();
+    NVRX_TOPK_WINNERS(TOP, row, K, top, win);
 
     // wave v recomputes winners v, v + 4, ... from H and the samples and stores their outputs
     const int64_t stride = a.hist_stride ? a.hist_stride : K;
@@ -308,16 +214,7 @@ void seghist_select_kernel(RaggedSegs segs, nvrx_seghistattr_args a) {
             }
         }
         if (lane != 0) continue;
-        const bool taken = loss == loss;
-        const int64_t o = r * a.top + j;
-        const double qnan = __builtin_nan("");
-        a.idx[o] = taken ? col : -1;
-        a.loss[o] = taken ? loss : qnan;
-        a.tail_ns[o] = taken ? tail : 0ull;
-        a.total_ns[o] = taken ? total : 0ull;
-        a.tail_calls[o] = taken ? calls : 0u;
-        a.thr_bucket[o] = taken ? T : -1;
-        a.base_share[o] = taken ? share : qnan;
+        store_winner(a, r * a.top + j, loss == loss, col, loss, tail, total, calls, T, share);
     }
 }
 
@@ -327,26 +224,15 @@ void seghist_select_kernel(RaggedSegs segs, nvrx_seghistattr_args a) {
 hipError_t segment_history_attribution_ragged(const nvrx_seghistattr_args& a, hipStream_t st) {
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
     if (a.top < 1 || a.top > NVRX_MAX_ATTRIBUTION) return hipErrorInvalidValue;
-    // the split rule of segment_history_scores_ragged: about SHA_TARGET_WGS workgroups over rows x
-    // splits, a split no shorter than one workgroup trip (SHA_TRIP kernels) and a whole number of
-    // trips
-    int64_t splits = (SHA_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + SHA_TRIP - 1) / SHA_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + SHA_TRIP - 1) / SHA_TRIP * SHA_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= SHA_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, SHA_TRIP, SHA_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     const dim3 rows((unsigned)a.R), b(256);
     const RaggedSegs segs{a.ns, a.seg_off, a.seg_len, a.cap};
     hipLaunchKernelGGL(seghist_loss_kernel, grid, dim3(SHA_THREADS), 0, st, segs, a, kper);
-    if (a.top <= 1)
-        hipLaunchKernelGGL(seghist_select_kernel<1>, rows, b, 0, st, segs, a);
-    else if (a.top <= 4)
-        hipLaunchKernelGGL(seghist_select_kernel<4>, rows, b, 0, st, segs, a);
-    else if (a.top <= 8)
-        hipLaunchKernelGGL(seghist_select_kernel<8>, rows, b, 0, st, segs, a);
-    else
-        hipLaunchKernelGGL(seghist_select_kernel<16>, rows, b, 0, st, segs, a);
+    dispatch_top(a.top, [&](auto t) {
+        hipLaunchKernelGGL(seghist_select_kernel<decltype(t)::value>, rows, b, 0, st, segs, a);
+    });
     return hipGetLastError();
 }
 

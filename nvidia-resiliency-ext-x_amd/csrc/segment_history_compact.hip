@@ -35,11 +35,12 @@
 //                      Row sums and folded: DPP + LDS reduction, the non-zero sums added with
 //                      64-bit device atomics (cleared by a kernel on the stream first).  Integer
 //                      adds are exact in any order: the result is the same on every run.
-//   segchist_finalize  the three separately rounded f64 operations and strag, as seghist_finalize.
-// bucket_of, count_wave, the clear and the finalize restate what segment_history.hip holds in its
-// anonymous namespace; the element's load and decode, sat_add and lds_order live in chist_wave.h,
-// shared with histogram_history_compact.hip.  Every loop is bounded by K, by the
-// retained length or by 12.  No kernel uses scratch memory (make asm).
+//   tail_score_finalize_kernel<nvrx_segchist_args>   the three separately rounded f64 operations
+//                      and strag (histogram_wave.h, as the clear, clear4_folded_kernel).
+// bucket_of, sat_add, count_wave and slot_of are histogram_wave.h's too; the element's load and
+// decode and lds_order live in chist_wave.h, shared with histogram_history_compact.hip and
+// segment_history_compact_attribution.hip.  Every loop is bounded by K, by the retained length or
+// by 12.  No kernel uses scratch memory (make asm).
 
 #include "chist_wave.h"
 #include "segment_addr.h"
@@ -60,40 +61,6 @@ constexpr unsigned SC_NONE = HB;                 // the bucket of a lane past th
 static_assert(SC_WORDS == 16 && SC_UNROLL * SC_WORDS == NVRX_WAVE, "an element is one DPP row");
 static_assert(SC_HW == HB + SC_WORDS && SC_HW == 4 * NVRX_WAVE, "one 16-byte vector per lane clears it");
 static_assert(4 * SC_E + SC_E + 4 == NVRX_CHIST_BYTES, "count[12], bucket[12], n");
-
-// segment_histogram.hip's bucket expression: sh = e - 3 for x >= 8, 0 below
-__device__ __forceinline__ unsigned bucket_of(unsigned x) {
-    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
-    return (sh << 3) + (x >> sh);
-}
-
-// 64 buckets, one per lane (SC_NONE: no sample), into the wave's bins h
-__device__ __forceinline__ void count_wave(unsigned b, unsigned* h) {
-    uint64_t live = __ballot(b != SC_NONE);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        if (!live) return;  // wave-uniform
-        const int l = __builtin_ctzll(live);
-        const unsigned lead = rl(b, l);
-        const uint64_t same = __ballot(b == lead);
-        if (lane_id() == l) atomicAdd(&h[lead], (unsigned)__popcll(same));
-        live &= ~same;
-    }
-    if ((live >> lane_id()) & 1) atomicAdd(&h[b], 1u);
-}
-
-__global__ __launch_bounds__(256)
-void segchist_clear_kernel(u64* a, u64* b, u64* c, u64* d, u64* folded, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    if (a) {  // SCORE
-        a[i] = 0ull;
-        b[i] = 0ull;
-        c[i] = 0ull;
-        d[i] = 0ull;
-    }
-    if (folded) folded[i] = 0ull;  // UPDATE
-}
 
 // kernels [blockIdx.y * kper, + kper) of row blockIdx.x
 template <bool SCORE, bool UPDATE, bool CALLS>
@@ -128,8 +95,7 @@ void segchist_kernel(RaggedSegs segs, nvrx_segchist_args a, int64_t kper) {
             run[u] = nullptr;
             len[u] = 0;
             if (k < ke) {
-                int64_t s = a.hist_index ? (int64_t)a.hist_index[k] : k;
-                if (a.col_valid && !a.col_valid[k]) s = -1;
+                int64_t s = slot_of(a, k);
                 if (s >= 0) segs.get(r * K + k, run[u], len[u]);
                 if (len[u] <= 0) s = -1;  // an empty element: no score, no update, no read of the history
                 slot[u] = s;
@@ -193,7 +159,7 @@ void segchist_kernel(RaggedSegs segs, nvrx_segchist_args a, int64_t kper) {
                             tail += hit ? w : 0ull;
                             if (CALLS) calls += (unsigned)__popcll(__ballot(hit));
                         }
-                        if (count) count_wave(live ? b : SC_NONE, hb);
+                        if (count) count_wave<SC_NONE>(live ? b : SC_NONE, hb);
                     }
                 }
             }
@@ -282,21 +248,6 @@ void segchist_kernel(RaggedSegs segs, nvrx_segchist_args a, int64_t kper) {
     if (v) atomicAdd((u64*)dst + r, v);
 }
 
-__global__ __launch_bounds__(256) void segchist_finalize_kernel(nvrx_segchist_args a) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= a.R) return;
-    const u64 tl = a.tail_ns[r], tt = a.total_ns[r], bl = a.base_tail_ns[r], bt = a.base_total_ns[r];
-    double score = __builtin_nan("");
-    if (tt != 0 && bt != 0) {
-        const double share = (double)tl / (double)tt;
-        const double bs = (double)bl / (double)bt;
-        const double den = 1.0 - bs;
-        if (den != 0.0) score = (1.0 - share) / den;
-    }
-    a.score[r] = score;
-    if (a.strag) a.strag[r] = score < a.score_thr;  // NaN compares false
-}
-
 template <bool SCORE, bool UPDATE, bool CALLS>
 void launch_segchist(const nvrx_segchist_args& a, dim3 grid, int64_t kper, hipStream_t st) {
     hipLaunchKernelGGL((segchist_kernel<SCORE, UPDATE, CALLS>), grid, dim3(SC_THREADS), 0, st,
@@ -309,16 +260,11 @@ void launch_segchist(const nvrx_segchist_args& a, dim3 grid, int64_t kper, hipSt
 hipError_t segment_history_scores_compact_ragged(const nvrx_segchist_args& a, hipStream_t st) {
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
     const bool score = a.mode & NVRX_HTAIL_SCORE, update = a.mode & NVRX_HTAIL_UPDATE;
-    // the split rule of segment_history.hip: about SC_TARGET_WGS workgroups over rows x splits, a
-    // split no shorter than one workgroup trip (SC_TRIP kernels) and a whole number of trips
-    int64_t splits = (SC_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + SC_TRIP - 1) / SC_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + SC_TRIP - 1) / SC_TRIP * SC_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= SC_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, SC_TRIP, SC_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     const dim3 rows((unsigned)((a.R + 255) / 256));
-    hipLaunchKernelGGL(segchist_clear_kernel, rows, dim3(256), 0, st,
+    hipLaunchKernelGGL(clear4_folded_kernel<u64>, rows, dim3(256), 0, st,
                        score ? (u64*)a.tail_ns : nullptr, (u64*)a.total_ns, (u64*)a.base_tail_ns,
                        (u64*)a.base_total_ns, update ? (u64*)a.folded : nullptr, a.R);
     if (!score)
@@ -329,7 +275,8 @@ hipError_t segment_history_scores_compact_ragged(const nvrx_segchist_args& a, hi
     else
         a.tail_calls ? launch_segchist<true, false, true>(a, grid, kper, st)
                      : launch_segchist<true, false, false>(a, grid, kper, st);
-    if (score) hipLaunchKernelGGL(segchist_finalize_kernel, rows, dim3(256), 0, st, a);
+    if (score)
+        hipLaunchKernelGGL(tail_score_finalize_kernel<nvrx_segchist_args>, rows, dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -40,15 +40,12 @@
 //          population count, and lane 0 stores every per-winner output.  What is stored comes
 //          from the inputs, the key only orders.
 // Every (r, k) has one owner: no atomics, no scratch, no clear, no LDS in the loss kernel.
-// bucket_of, row_incl_scan_u64, the masked sample load and `excess` restate what
-// segment_history_compact.hip and segment_history_attribution.hip hold in their anonymous
-// namespaces; no existing file changes.  Every loop is bounded by K or a retained length (an
-// element's 12 entries are lanes, not iterations).  No kernel uses scratch memory (make asm;
-// DESIGN 3.19).
+// bucket_of, slot_of and `excess` are histogram_wave.h's, row_incl_scan_u64 chist_wave.h's; the
+// select's first half (NVRX_TOPK_WINNERS), the winner's stores and the choice of TOP are
+// topk_select.h's.  Every loop is bounded by K or a retained length (an element's 12 entries are
+// lanes, not iterations).  No kernel uses scratch memory (make asm).
 
-#include <type_traits>
-
-#include "histogram_wave.h"
+#include "chist_wave.h"
 #include "segment_addr.h"
 #include "topk_select.h"
 
@@ -65,21 +62,6 @@ constexpr int SCA_E = NVRX_CHIST_ENTRIES;
 constexpr int SCA_WORDS = NVRX_CHIST_BYTES / 4;    // 16: one DPP row
 static_assert(SCA_WORDS == 16 && SCA_UNROLL * SCA_WORDS == NVRX_WAVE, "an element is one DPP row");
 static_assert(4 * SCA_E + SCA_E + 4 == NVRX_CHIST_BYTES, "count[12], bucket[12], n");
-
-// segment_histogram.hip's bucket expression: sh = e - 3 for x >= 8, 0 below
-__device__ __forceinline__ unsigned bucket_of(unsigned x) {
-    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
-    return (sh << 3) + (x >> sh);
-}
-
-// inclusive u64 prefix inside each 16-lane row (row_shr zero-fills at the row's start)
-__device__ __forceinline__ u64 row_incl_scan_u64(u64 v) {
-    v += dpp_u64<0x111>(v);
-    v += dpp_u64<0x112>(v);
-    v += dpp_u64<0x114>(v);
-    v += dpp_u64<0x118>(v);
-    return v;
-}
 
 // the sum of each 16-lane row in every lane of the row: the DPP steps of wave_sum_u64
 __device__ __forceinline__ u64 row_sum_u64(u64 v) {
@@ -172,20 +154,6 @@ __device__ __forceinline__ Walk walk(const uint32_t* q, int m, int t, int lane) 
     return p;
 }
 
-// the three f64 operations of the definition, each rounded separately (-ffp-contract=off): both
-// kernels call it, so a winner's stored loss is the loss that ranked it
-__device__ __forceinline__ double excess(u64 tail, u64 total, u64 btail, u64 btotal, double& share) {
-    share = (double)btail / (double)btotal;
-    return (double)tail - (double)total * share;
-}
-
-// slot of column k (wave-uniform), -1 where the column is not eligible
-__device__ __forceinline__ int64_t slot_of(const nvrx_segchistattr_args& a, int64_t k) {
-    int64_t s = a.hist_index ? (int64_t)a.hist_index[k] : k;
-    if (a.col_valid && !a.col_valid[k]) s = -1;
-    return s;
-}
-
 // kernels [blockIdx.y * kper, + kper) of row blockIdx.x
 __global__ __launch_bounds__(SCA_THREADS)
 void segchist_loss_kernel(RaggedSegs segs, nvrx_segchistattr_args a, int64_t kper) {
@@ -251,76 +219,14 @@ void segchist_loss_kernel(RaggedSegs segs, nvrx_segchistattr_args a, int64_t kpe
 template <int TOP>
 __global__ __launch_bounds__(256)
 void segchist_select_kernel(RaggedSegs segs, nvrx_segchistattr_args a) {
-    __shared__ uint64_t best_k[2][4];
-    __shared__ int32_t best_c[2][4];
-    __shared__ int32_t win[NVRX_MAX_ATTRIBUTION];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int64_t r = blockIdx.x;
     const int64_t K = a.K;
     const double* __restrict__ row = a.loss_all + r * K;
-
-    // this thread's candidates, best first; every index below is a compile-time constant
-    uint64_t ck[TOP];
-    int32_t cc[TOP];
-#pragma unroll
-    for (int i = 0; i < TOP; ++i) {
-        ck[i] = 0;
-        cc[i] = NO_COL;
-    }
-    constexpr int SC = 8;  // every load of a batch is issued before any is used
-    // FIRST: the thread's first batch, whose element c finds at most c candidates held
-    auto batch = [&](const int64_t k0, auto first) {
-        constexpr bool FIRST = decltype(first)::value;
-        double v[SC];
-#pragma unroll
-        for (int c = 0; c < SC; ++c) {
-            const int64_t k = k0 + c * 256;
-            v[c] = k < K ? row[k] : __builtin_nan("");
-        }
-#pragma unroll
-        for (int c = 0; c < SC; ++c) {
-            const uint64_t key = v[c] == v[c] ? loss_key(v[c]) : 0ull;  // NaN: not taken
-            const int32_t col = (int32_t)(k0 + c * 256);
-            const int n = FIRST && c + 1 < TOP ? c + 1 : TOP;  // positions from n on are empty
-            if (__builtin_amdgcn_ballot_w64(key > ck[n - 1]) == 0) continue;  // wave-uniform skip
-            NVRX_TOPK_INSERT(TOP, ck, cc, key, col, n);
-        }
-    };
-    batch(tid, std::true_type{});
-    for (int64_t k0 = (int64_t)tid + 256 * SC; k0 < K; k0 += 256 * SC) batch(k0, std::false_type{});
-
-    // `top` rounds of workgroup argmax over the threads' heads
     const int top = a.top < TOP ? a.top : TOP;
-    for (int j = 0; j < top; ++j) {
-        uint64_t k = ck[0];
-        int32_t c = cc[0];
-        wave_best(k, c);
-        const int b = j & 1;
-        if (lane == 0) {
-            best_k[b][wave] = k;
-            best_c[b][wave] = c;
-        }
-        __syncthreads();
-        uint64_t wk = best_k[b][0];
-        int32_t wc = best_c[b][0];
-#pragma unroll
-        for (int v = 1; v < 4; ++v) {
-            const uint64_t ok = best_k[b][v];
-            const int32_t oc = best_c[b][v];
-            const bool take = before(ok, oc, wk, wc);
-            wk = take ? ok : wk;
-            wc = take ? oc : wc;
-        }
-        if (tid == 0) win[j] = wk != 0 ? wc : -1;
-        // the winner pops its head (columns are distinct, so one thread at most holds wc); the
-        // three waves without it skip the shift
-        const bool pop = wk != 0 && cc[0] == wc;
-        if (__builtin_amdgcn_ballot_w64(pop) == 0) continue;
-        NVRX_TOPK_POP(TOP, ck, cc, pop);
-    }
-    __syncthreads();
+    NVRX_TOPK_WINNERS(TOP, row, K, top, win);
 
     // wave v recomputes winners v, v + 4, ... from the element and the samples and stores their
     // outputs
@@ -353,16 +259,7 @@ void segchist_select_kernel(RaggedSegs segs, nvrx_segchistattr_args a) {
             }
         }
         if (lane != 0) continue;
-        const bool taken = loss == loss;
-        const int64_t o = r * a.top + j;
-        const double qnan = __builtin_nan("");
-        a.idx[o] = taken ? col : -1;
-        a.loss[o] = taken ? loss : qnan;
-        a.tail_ns[o] = taken ? tail : 0ull;
-        a.total_ns[o] = taken ? total : 0ull;
-        a.tail_calls[o] = taken ? calls : 0u;
-        a.thr_bucket[o] = taken ? T : -1;
-        a.base_share[o] = taken ? share : qnan;
+        store_winner(a, r * a.top + j, loss == loss, col, loss, tail, total, calls, T, share);
     }
 }
 
@@ -372,26 +269,15 @@ void segchist_select_kernel(RaggedSegs segs, nvrx_segchistattr_args a) {
 hipError_t segment_history_attribution_compact_ragged(const nvrx_segchistattr_args& a, hipStream_t st) {
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
     if (a.top < 1 || a.top > NVRX_MAX_ATTRIBUTION) return hipErrorInvalidValue;
-    // the split rule of segment_history_scores_compact_ragged: about SCA_TARGET_WGS workgroups
-    // over rows x splits, a split no shorter than one workgroup trip (SCA_TRIP kernels) and a
-    // whole number of trips
-    int64_t splits = (SCA_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + SCA_TRIP - 1) / SCA_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + SCA_TRIP - 1) / SCA_TRIP * SCA_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= SCA_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, SCA_TRIP, SCA_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     const dim3 rows((unsigned)a.R), b(256);
     const RaggedSegs segs{a.ns, a.seg_off, a.seg_len, a.cap};
     hipLaunchKernelGGL(segchist_loss_kernel, grid, dim3(SCA_THREADS), 0, st, segs, a, kper);
-    if (a.top <= 1)
-        hipLaunchKernelGGL(segchist_select_kernel<1>, rows, b, 0, st, segs, a);
-    else if (a.top <= 4)
-        hipLaunchKernelGGL(segchist_select_kernel<4>, rows, b, 0, st, segs, a);
-    else if (a.top <= 8)
-        hipLaunchKernelGGL(segchist_select_kernel<8>, rows, b, 0, st, segs, a);
-    else
-        hipLaunchKernelGGL(segchist_select_kernel<16>, rows, b, 0, st, segs, a);
+    dispatch_top(a.top, [&](auto t) {
+        hipLaunchKernelGGL(segchist_select_kernel<decltype(t)::value>, rows, b, 0, st, segs, a);
+    });
     return hipGetLastError();
 }
 

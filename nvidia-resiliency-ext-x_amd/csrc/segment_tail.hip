@@ -47,33 +47,7 @@
 namespace nvrx {
 namespace {
 
-constexpr int ST_LANE_MAX = 16;  // the longest retained run a lane walks alone
-constexpr int ST_UNROLL = 4;     // loads in flight per lane
 constexpr unsigned ST_NONE = HB; // the bucket of a slot past the segment's end
-
-// segment_histogram.hip's bucket expression: sh = e - 3 for x >= 8, 0 below
-__device__ __forceinline__ unsigned bucket_of(unsigned x) {
-    const unsigned sh = 28u - (unsigned)__builtin_clz(x | 8u);
-    return (sh << 3) + (x >> sh);
-}
-
-__device__ __forceinline__ const uint32_t* rl_ptr(const uint32_t* p, int l) {
-    const uint64_t b = (uint64_t)(uintptr_t)p;
-    return (const uint32_t*)(uintptr_t)(((uint64_t)rl((unsigned)(b >> 32), l) << 32) | rl((unsigned)b, l));
-}
-
-// samples [base, base + 64 ST_UNROLL) of a segment of m, 64 consecutive ones per load; a lane past
-// the end re-reads the last sample (its slot is then masked by the caller)
-__device__ __forceinline__ void wave_load(const uint32_t* q, int m, int base, unsigned (&x)[ST_UNROLL]) {
-#pragma unroll
-    for (int u = 0; u < ST_UNROLL; ++u)
-        x[u] = __builtin_nontemporal_load(q + min(base + u * 64 + lane_id(), m - 1));
-}
-// samples [i, i + ST_UNROLL) of a lane's own segment of n
-__device__ __forceinline__ void lane_load(const uint32_t* p, int n, int i, unsigned (&x)[ST_UNROLL]) {
-#pragma unroll
-    for (int u = 0; u < ST_UNROLL; ++u) x[u] = p[min(i + u, n - 1)];
-}
 
 __global__ __launch_bounds__(256) void clear2_u64_kernel(u64* a, u64* b, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -93,21 +67,6 @@ constexpr int SF_STRIDE = HB + 1;                  // LDS words per column: odd,
                                                    // wave start on different banks
 constexpr int SF_TARGET_WGS = 2048;                // 256 CUs x 8 workgroups
 static_assert((SF_COLS & (SF_COLS - 1)) == 0 && 64 % SF_COLS == 0, "columns per wave");
-
-// 64 buckets, one per lane (ST_NONE: no sample), into the column's bins h
-__device__ __forceinline__ void count_wave(unsigned b, unsigned* h) {
-    uint64_t live = __ballot(b != ST_NONE);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        if (!live) return;  // wave-uniform
-        const int l = __builtin_ctzll(live);
-        const unsigned lead = rl(b, l);
-        const uint64_t same = __ballot(b == lead);
-        if (lane_id() == l) atomicAdd(&h[lead], (unsigned)__popcll(same));
-        live &= ~same;
-    }
-    if ((live >> lane_id()) & 1) atomicAdd(&h[b], 1u);
-}
 
 __global__ __launch_bounds__(SF_THREADS)
 void segment_fleet_kernel(RaggedSegs segs, int64_t R, int64_t K, int64_t nbx, int64_t rows_per, u64* fleet) {
@@ -158,7 +117,7 @@ void segment_fleet_kernel(RaggedSegs segs, int64_t R, int64_t K, int64_t nbx, in
 #pragma unroll
                 for (int u = 0; u < ST_UNROLL; ++u) {
                     if (base + u * 64 >= m) break;  // wave-uniform
-                    count_wave(base + u * 64 + lane < m ? bucket_of(x[u]) : ST_NONE, hl);
+                    count_wave<ST_NONE>(base + u * 64 + lane < m ? bucket_of(x[u]) : ST_NONE, hl);
                 }
             }
         }
@@ -179,19 +138,6 @@ constexpr int TT_WAVES = TT_THREADS / 64;
 constexpr int TT_TRIP = TT_THREADS;  // columns per workgroup trip: a split's granule
 constexpr int TT_TARGET_WGS = 2048;
 
-struct TailAcc {
-    u64 total = 0, tail = 0;
-    unsigned calls = 0;
-    __device__ __forceinline__ void add(unsigned x, int t) {
-        const int b = (int)bucket_of(x);
-        const u64 w = weight_of(b);
-        const bool hit = b > t;
-        total += w;
-        tail += hit ? w : 0ull;
-        calls += hit;
-    }
-};
-
 // columns [blockIdx.y * kper, + kper) of row blockIdx.x
 template <bool CALLS>
 __global__ __launch_bounds__(TT_THREADS)
@@ -203,7 +149,7 @@ void segment_tail_kernel(RaggedSegs segs, nvrx_segtail_args a, int64_t kper) {
     const int64_t K = a.K;
     const int64_t ks = (int64_t)blockIdx.y * kper;
     const int64_t ke = min(K, ks + kper);
-    TailAcc acc;
+    TailAcc<true> acc;  // the calls are dead code without CALLS
     for (int64_t kb = ks + wave * 64; kb < ke; kb += TT_TRIP) {  // wave-uniform
         const int64_t k = kb + lane;
         int T = -1, n = 0;
@@ -306,13 +252,8 @@ hipError_t segment_fleet_histogram_ragged(const uint32_t* ns, const int64_t* seg
 
 hipError_t segment_tail_scores_ragged(const nvrx_segtail_args& a, hipStream_t st) {
     if (a.R <= 0 || a.K <= 0) return hipSuccess;
-    // the split rule of histogram_history.hip: about TT_TARGET_WGS workgroups over rows x splits, a
-    // split no shorter than one workgroup trip and a whole number of trips
-    int64_t splits = (TT_TARGET_WGS + a.R - 1) / a.R;
-    splits = min(splits, (a.K + TT_TRIP - 1) / TT_TRIP);
-    int64_t kper = (a.K + splits - 1) / splits;
-    kper = (kper + TT_TRIP - 1) / TT_TRIP * TT_TRIP;
-    splits = (a.K + kper - 1) / kper;  // <= TT_TARGET_WGS: fits grid.y
+    int64_t kper;
+    const int64_t splits = row_splits(a.R, a.K, TT_TRIP, TT_TARGET_WGS, &kper);
     const dim3 grid((unsigned)a.R, (unsigned)splits);
     const dim3 rows((unsigned)((a.R + 255) / 256));
     const RaggedSegs segs{a.ns, a.seg_off, a.seg_len, a.cap};

@@ -1,8 +1,12 @@
 // topk_select.h -- what the two top-k kernels share (attribution.hip: the kernels behind a GPU
 // score; histogram_attribution.hip: the kernels behind a tail score): an order-preserving 64-bit
 // key of an f64 loss, the per-thread sorted candidate list in registers (insert / pop), and the
-// wave argmax over (key, column) on DPP.
+// wave argmax over (key, column) on DPP.  For the four tail attributions (histogram_attribution,
+// segment_tail_attribution, segment_history_attribution, segment_history_compact_attribution) also
+// the select's first half (NVRX_TOPK_WINNERS), the winner's stores and the host's choice of TOP.
 #pragma once
+#include <type_traits>
+
 #include "nvrx_common.h"
 
 namespace nvrx {
@@ -95,3 +99,113 @@ __device__ __forceinline__ void wave_best(uint64_t& k, int32_t& c) {
         ck[TOP - 1] = (pop) ? 0ull : ck[TOP - 1];                         \
         cc[TOP - 1] = (pop) ? NO_COL : cc[TOP - 1];                       \
     } while (0)
+
+// The select of the tail attributions, by one 256-thread workgroup: the columns of the `top`
+// (<= TOP) largest losses of row[0, K) (const double*), best first, into win[] in LDS; -1 where
+// fewer are taken (a NaN loss is not).  Ties go to the lower column.  Ends with a workgroup
+// barrier: every thread may read win[] afterwards.  It declares the kernel's LDS (best_k, best_c:
+// the two rounds' per-wave bests; win) and reads the kernel's tid, wave and lane.
+//
+// A statement macro like the two steps above, and for their reason: as a __forceinline__ function
+// each select kernel kept its register, LDS and occupancy figures but not its instructions (the
+// order of the LDS arrays, and the exit test of the rounds' loop inverted); expanded in place the
+// four select kernels' assembly is what it was with this block written out in each.
+//   per thread: candidates best first, every index a compile-time constant; batches of SC = 8
+//   loads, all issued before any is used; FIRST: the thread's first batch, whose element c finds
+//   at most c candidates held (positions from n on are empty); a NaN is not taken; the insert is
+//   skipped where no lane's key beats position n - 1 (wave-uniform).
+//   then `top` rounds of workgroup argmax over the threads' heads: the winner pops its head
+//   (columns are distinct, so one thread at most holds wc); the three waves without it skip the
+//   shift.
+#define NVRX_TOPK_WINNERS(TOP, row, K, top, win)                                                   \
+    __shared__ uint64_t best_k[2][4];                                                              \
+    __shared__ int32_t best_c[2][4];                                                               \
+    __shared__ int32_t win[NVRX_MAX_ATTRIBUTION];                                                  \
+    do {                                                                                           \
+        uint64_t ck[TOP];                                                                          \
+        int32_t cc[TOP];                                                                           \
+        _Pragma("unroll") for (int i = 0; i < TOP; ++i) {                                          \
+            ck[i] = 0;                                                                             \
+            cc[i] = NO_COL;                                                                        \
+        }                                                                                          \
+        constexpr int SC = 8;                                                                      \
+        auto batch = [&](const int64_t k0, auto first) {                                           \
+            constexpr bool FIRST = decltype(first)::value;                                         \
+            double v[SC];                                                                          \
+            _Pragma("unroll") for (int c = 0; c < SC; ++c) {                                       \
+                const int64_t k = k0 + c * 256;                                                    \
+                v[c] = k < (K) ? (row)[k] : __builtin_nan("");                                     \
+            }                                                                                      \
+            _Pragma("unroll") for (int c = 0; c < SC; ++c) {                                       \
+                const uint64_t key = v[c] == v[c] ? loss_key(v[c]) : 0ull;                         \
+                const int32_t col = (int32_t)(k0 + c * 256);                                       \
+                const int n = FIRST && c + 1 < TOP ? c + 1 : TOP;                                  \
+                if (__builtin_amdgcn_ballot_w64(key > ck[n - 1]) == 0) continue;                   \
+                NVRX_TOPK_INSERT(TOP, ck, cc, key, col, n);                                        \
+            }                                                                                      \
+        };                                                                                         \
+        batch(tid, std::true_type{});                                                              \
+        for (int64_t k0 = (int64_t)tid + 256 * SC; k0 < (K); k0 += 256 * SC)                       \
+            batch(k0, std::false_type{});                                                          \
+        for (int j = 0; j < (top); ++j) {                                                          \
+            uint64_t k = ck[0];                                                                    \
+            int32_t c = cc[0];                                                                     \
+            wave_best(k, c);                                                                       \
+            const int b = j & 1;                                                                   \
+            if (lane == 0) {                                                                       \
+                best_k[b][wave] = k;                                                               \
+                best_c[b][wave] = c;                                                               \
+            }                                                                                      \
+            __syncthreads();                                                                       \
+            uint64_t wk = best_k[b][0];                                                            \
+            int32_t wc = best_c[b][0];                                                             \
+            _Pragma("unroll") for (int v = 1; v < 4; ++v) {                                        \
+                const uint64_t ok = best_k[b][v];                                                  \
+                const int32_t oc = best_c[b][v];                                                   \
+                const bool take = before(ok, oc, wk, wc);                                          \
+                wk = take ? ok : wk;                                                               \
+                wc = take ? oc : wc;                                                               \
+            }                                                                                      \
+            if (tid == 0) win[j] = wk != 0 ? wc : -1;                                              \
+            const bool pop = wk != 0 && cc[0] == wc;                                               \
+            if (__builtin_amdgcn_ballot_w64(pop) == 0) continue;                                   \
+            NVRX_TOPK_POP(TOP, ck, cc, pop);                                                       \
+        }                                                                                          \
+        __syncthreads();                                                                           \
+    } while (0)
+
+namespace nvrx {
+namespace {
+
+// what a select kernel stores for winner slot o of its args: the terms when taken, else the empty
+// slot
+template <typename Args>
+__device__ __forceinline__ void store_winner(const Args& a, int64_t o, bool taken, int col, double loss,
+                                             uint64_t tail, uint64_t total, unsigned calls, int T,
+                                             double share) {
+    const double qnan = __builtin_nan("");
+    a.idx[o] = taken ? col : -1;
+    a.loss[o] = taken ? loss : qnan;
+    a.tail_ns[o] = taken ? tail : 0ull;
+    a.total_ns[o] = taken ? total : 0ull;
+    a.tail_calls[o] = taken ? calls : 0u;
+    a.thr_bucket[o] = taken ? T : -1;
+    a.base_share[o] = taken ? share : qnan;
+}
+
+// Host side: f(std::integral_constant<int, TOP>) with the smallest TOP of 1 / 4 / 8 / 16 that
+// holds `top`
+template <typename F>
+inline void dispatch_top(int top, F&& f) {
+    if (top <= 1)
+        f(std::integral_constant<int, 1>{});
+    else if (top <= 4)
+        f(std::integral_constant<int, 4>{});
+    else if (top <= 8)
+        f(std::integral_constant<int, 8>{});
+    else
+        f(std::integral_constant<int, 16>{});
+}
+
+}  // namespace
+}  // namespace nvrx

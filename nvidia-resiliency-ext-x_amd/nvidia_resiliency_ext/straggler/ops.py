@@ -493,6 +493,70 @@ def _u8_vector(t, name, n):
     return t
 
 
+def _history_request(fn, permille, score, update):
+    """(pm, mode) of an individual-score call; ``fn`` prefixes the message."""
+    pm = tail_permille(permille)
+    if not (score or update):
+        raise ValueError(f"{fn}: at least one of score and update")
+    return pm, (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+
+
+def _history_slots(R, K, history, hist_stride, hist_index, col_valid, skip_rows=None, *, compact):
+    """Checks the history of R rows x K columns -- dense ``hist`` or compact ``chist`` -- and what
+    addresses it; returns the stride."""
+    stride = int(hist_stride)
+    if stride < 0 or (stride and hist_index is None and stride < K):
+        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
+    if compact:
+        N.require_device(history, "chist")
+        if history.dtype != torch.uint8 or history.data_ptr() % 16:
+            raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor")
+        _tail_tensor(history, "chist", torch.uint8, (R, stride or K, N.CHIST_BYTES))
+    else:
+        N.require_device(history, "hist")
+        if history.dtype not in (torch.int32, torch.uint32) or history.data_ptr() % 16:
+            raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
+        _tail_tensor(history, "hist", history.dtype, (R, stride or K, N.HIST_BINS))
+    if hist_index is not None:
+        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
+    _u8_vector(col_valid, "col_valid", K)
+    _u8_vector(skip_rows, "skip_rows", R)
+    return stride
+
+
+def _history_outputs(R, K, d, score, out, tail_calls):
+    """(out, calls): the checked (or new) outputs of an individual score and its tail_calls."""
+    calls = None
+    if score:
+        if out is None:
+            out = HistoryTailScores.empty(R, d)
+        _tail_tensor(out.score, "out.score", torch.float64, (R,))
+        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
+            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
+        if out.strag is not None:
+            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
+        if tail_calls is True:
+            calls = out.tail_calls
+            if calls is None:
+                calls = torch.empty((R, K), dtype=torch.int32, device=d)
+        elif tail_calls is not False and tail_calls is not None:
+            calls = tail_calls
+        if calls is not None:
+            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
+    elif out is None:
+        out = HistoryTailScores()
+    return out, calls
+
+
+def _folded(R, d, update, folded):
+    if not update:
+        return None
+    if folded is None:
+        folded = torch.empty(R, dtype=torch.int64, device=d)
+    _tail_tensor(folded, "folded", torch.int64, (R,))
+    return folded
+
+
 def histogram_history_scores(counts: torch.Tensor, hist: torch.Tensor, *, permille: int,
                              score: bool = True, update: bool = True,
                              hist_index: Optional[torch.Tensor] = None, hist_stride: int = 0,
@@ -516,42 +580,11 @@ def histogram_history_scores(counts: torch.Tensor, hist: torch.Tensor, *, permil
     share a slot and ``counts`` must not overlap ``hist`` (neither is checked).
     ``tail_calls=True`` (or an int32 [R, K] tensor) also counts the calls above T per row and
     kernel.  ``score=False`` touches no score output.  ``out``: preallocated outputs."""
-    pm = tail_permille(permille)
-    if not (score or update):
-        raise ValueError("histogram_history_scores: at least one of score and update")
+    pm, mode = _history_request("histogram_history_scores", permille, score, update)
     R, K = _tail_counts(counts)
     d = counts.device
-    stride = int(hist_stride)
-    if stride < 0 or (stride and hist_index is None and stride < K):
-        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
-    N.require_device(hist, "hist")
-    if hist.dtype not in (torch.int32, torch.uint32) or hist.data_ptr() % 16:
-        raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
-    _tail_tensor(hist, "hist", hist.dtype, (R, stride or K, N.HIST_BINS))
-    if hist_index is not None:
-        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
-    _u8_vector(col_valid, "col_valid", K)
-    _u8_vector(skip_rows, "skip_rows", R)
-    calls = None
-    if score:
-        if out is None:
-            out = HistoryTailScores.empty(R, d)
-        _tail_tensor(out.score, "out.score", torch.float64, (R,))
-        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
-            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
-        if out.strag is not None:
-            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
-        if tail_calls is True:
-            calls = out.tail_calls
-            if calls is None:
-                calls = torch.empty((R, K), dtype=torch.int32, device=d)
-        elif tail_calls is not False and tail_calls is not None:
-            calls = tail_calls
-        if calls is not None:
-            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
-    elif out is None:
-        out = HistoryTailScores()
-    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    stride = _history_slots(R, K, hist, hist_stride, hist_index, col_valid, skip_rows, compact=False)
+    out, calls = _history_outputs(R, K, d, score, out, tail_calls)
     a = N.HistTailArgs(R, K, counts.data_ptr(), hist.data_ptr(), stride, N.ptr(hist_index),
                        N.ptr(col_valid), N.ptr(skip_rows), pm, mode, float(score_thr),
                        N.ptr(out.tail_ns), N.ptr(out.total_ns), N.ptr(out.base_tail_ns),
@@ -577,42 +610,11 @@ def segment_history_scores_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
     that tensor.  An element without retained samples is not scored and leaves its history slot as
     it is.  ``hist`` keeps its format, so one history can be continued by either function; every
     other argument and ``out`` as in ``histogram_history_scores``."""
-    pm = tail_permille(permille)
-    if not (score or update):
-        raise ValueError("segment_history_scores_ragged: at least one of score and update")
+    pm, mode = _history_request("segment_history_scores_ragged", permille, score, update)
     R = _segment_rows(ns, seg_off, seg_len, K)
     d = ns.device
-    stride = int(hist_stride)
-    if stride < 0 or (stride and hist_index is None and stride < K):
-        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
-    N.require_device(hist, "hist")
-    if hist.dtype not in (torch.int32, torch.uint32) or hist.data_ptr() % 16:
-        raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
-    _tail_tensor(hist, "hist", hist.dtype, (R, stride or K, N.HIST_BINS))
-    if hist_index is not None:
-        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
-    _u8_vector(col_valid, "col_valid", K)
-    _u8_vector(skip_rows, "skip_rows", R)
-    calls = None
-    if score:
-        if out is None:
-            out = HistoryTailScores.empty(R, d)
-        _tail_tensor(out.score, "out.score", torch.float64, (R,))
-        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
-            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
-        if out.strag is not None:
-            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
-        if tail_calls is True:
-            calls = out.tail_calls
-            if calls is None:
-                calls = torch.empty((R, K), dtype=torch.int32, device=d)
-        elif tail_calls is not False and tail_calls is not None:
-            calls = tail_calls
-        if calls is not None:
-            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
-    elif out is None:
-        out = HistoryTailScores()
-    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    stride = _history_slots(R, K, hist, hist_stride, hist_index, col_valid, skip_rows, compact=False)
+    out, calls = _history_outputs(R, K, d, score, out, tail_calls)
     a = N.SegHistArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
                       int(aligned16), hist.data_ptr(), stride, N.ptr(hist_index), N.ptr(col_valid),
                       N.ptr(skip_rows), pm, mode, float(score_thr), N.ptr(out.tail_ns),
@@ -644,48 +646,12 @@ def segment_history_scores_compact_ragged(ns: torch.Tensor, seg_off: torch.Tenso
     stays 0 the history expands (``histograms.compact_to_dense``) to exactly the dense entry's and
     every output equals that entry's bit for bit.  A zeroed ``chist`` is the empty history.  Every
     other argument and ``out`` as in ``segment_history_scores_ragged``."""
-    pm = tail_permille(permille)
-    if not (score or update):
-        raise ValueError("segment_history_scores_compact_ragged: at least one of score and update")
+    pm, mode = _history_request("segment_history_scores_compact_ragged", permille, score, update)
     R = _segment_rows(ns, seg_off, seg_len, K)
     d = ns.device
-    stride = int(hist_stride)
-    if stride < 0 or (stride and hist_index is None and stride < K):
-        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
-    N.require_device(chist, "chist")
-    if chist.dtype != torch.uint8 or chist.data_ptr() % 16:
-        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor")
-    _tail_tensor(chist, "chist", torch.uint8, (R, stride or K, N.CHIST_BYTES))
-    if hist_index is not None:
-        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
-    _u8_vector(col_valid, "col_valid", K)
-    _u8_vector(skip_rows, "skip_rows", R)
-    calls = None
-    if score:
-        if out is None:
-            out = HistoryTailScores.empty(R, d)
-        _tail_tensor(out.score, "out.score", torch.float64, (R,))
-        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
-            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
-        if out.strag is not None:
-            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
-        if tail_calls is True:
-            calls = out.tail_calls
-            if calls is None:
-                calls = torch.empty((R, K), dtype=torch.int32, device=d)
-        elif tail_calls is not False and tail_calls is not None:
-            calls = tail_calls
-        if calls is not None:
-            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
-    elif out is None:
-        out = HistoryTailScores()
-    if update:
-        if folded is None:
-            folded = torch.empty(R, dtype=torch.int64, device=d)
-        _tail_tensor(folded, "folded", torch.int64, (R,))
-    else:
-        folded = None
-    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    stride = _history_slots(R, K, chist, hist_stride, hist_index, col_valid, skip_rows, compact=True)
+    out, calls = _history_outputs(R, K, d, score, out, tail_calls)
+    folded = _folded(R, d, update, folded)
     a = N.SegCHistArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
                        int(aligned16), chist.data_ptr(), stride, N.ptr(hist_index),
                        N.ptr(col_valid), N.ptr(skip_rows), pm, mode, float(score_thr),
@@ -718,48 +684,12 @@ def histogram_history_scores_compact(counts: torch.Tensor, chist: torch.Tensor, 
     equals that entry's bit for bit.  ``counts`` must not overlap ``chist``.  Every other argument
     and ``out`` as in ``histogram_history_scores``; ``histograms.compact_history_scores`` is the
     host twin."""
-    pm = tail_permille(permille)
-    if not (score or update):
-        raise ValueError("histogram_history_scores_compact: at least one of score and update")
+    pm, mode = _history_request("histogram_history_scores_compact", permille, score, update)
     R, K = _tail_counts(counts)
     d = counts.device
-    stride = int(hist_stride)
-    if stride < 0 or (stride and hist_index is None and stride < K):
-        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
-    N.require_device(chist, "chist")
-    if chist.dtype != torch.uint8 or chist.data_ptr() % 16:
-        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor")
-    _tail_tensor(chist, "chist", torch.uint8, (R, stride or K, N.CHIST_BYTES))
-    if hist_index is not None:
-        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
-    _u8_vector(col_valid, "col_valid", K)
-    _u8_vector(skip_rows, "skip_rows", R)
-    calls = None
-    if score:
-        if out is None:
-            out = HistoryTailScores.empty(R, d)
-        _tail_tensor(out.score, "out.score", torch.float64, (R,))
-        for n in ("tail_ns", "total_ns", "base_tail_ns", "base_total_ns"):
-            _tail_tensor(getattr(out, n), "out." + n, torch.int64, (R,))
-        if out.strag is not None:
-            _tail_tensor(out.strag, "out.strag", torch.uint8, (R,))
-        if tail_calls is True:
-            calls = out.tail_calls
-            if calls is None:
-                calls = torch.empty((R, K), dtype=torch.int32, device=d)
-        elif tail_calls is not False and tail_calls is not None:
-            calls = tail_calls
-        if calls is not None:
-            _tail_tensor(calls, "tail_calls", torch.int32, (R, K))
-    elif out is None:
-        out = HistoryTailScores()
-    if update:
-        if folded is None:
-            folded = torch.empty(R, dtype=torch.int64, device=d)
-        _tail_tensor(folded, "folded", torch.int64, (R,))
-    else:
-        folded = None
-    mode = (N.NVRX_HTAIL_SCORE if score else 0) | (N.NVRX_HTAIL_UPDATE if update else 0)
+    stride = _history_slots(R, K, chist, hist_stride, hist_index, col_valid, skip_rows, compact=True)
+    out, calls = _history_outputs(R, K, d, score, out, tail_calls)
+    folded = _folded(R, d, update, folded)
     a = N.HistCHistArgs(R, K, counts.data_ptr(), chist.data_ptr(), stride, N.ptr(hist_index),
                         N.ptr(col_valid), N.ptr(skip_rows), pm, mode, float(score_thr),
                         N.ptr(out.tail_ns), N.ptr(out.total_ns), N.ptr(out.base_tail_ns),
@@ -848,11 +778,7 @@ def compact_history_age(chist: torch.Tensor, shift: int = 1, evicted: Optional[t
     expansion of the result is ``histogram_history_age`` of the expansion
     (``histograms.compact_age`` on the host)."""
     s = age_shift(shift)
-    N.require_device(chist, "chist")
-    if (chist.dtype != torch.uint8 or chist.dim() != 3 or chist.shape[2] != N.CHIST_BYTES or
-            not chist.is_contiguous() or chist.data_ptr() % 16):
-        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor of shape [R, S, 64]")
-    R, S = chist.shape[0], chist.shape[1]
+    R, S = _compact_history(chist)
     if counts:
         if evicted is None:
             evicted = torch.empty(R, dtype=torch.int64, device=chist.device)
@@ -871,12 +797,8 @@ def histogram_history_age(hist: torch.Tensor, shift: int = 1, stream=None) -> to
     """Age a dense history ``hist`` (int32 [R, S, 240] holding u32 counts, changed in place and
     returned): every word becomes ``word >> shift`` (``histograms.history_age`` on the host)."""
     s = age_shift(shift)
-    N.require_device(hist, "hist")
-    if (hist.dtype not in (torch.int32, torch.uint32) or hist.dim() != 3 or
-            hist.shape[2] != N.HIST_BINS or not hist.is_contiguous() or hist.data_ptr() % 16):
-        raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor of shape [R, S, 240]")
-    N.call("nvrx_histogram_history_age", hist.data_ptr(), hist.shape[0], hist.shape[1], s,
-           _stream(stream))
+    R, S = _dense_history(hist)
+    N.call("nvrx_histogram_history_age", hist.data_ptr(), R, S, s, _stream(stream))
     return hist
 
 
@@ -949,6 +871,31 @@ class TailAttribution:
                 q[3].view(np.float64))
 
 
+def _attribution_outputs(R, K, top, d, out):
+    """The checked (or new) outputs of a tail attribution."""
+    if out is None:
+        out = TailAttribution.empty(R, K, top, d)
+    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
+                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
+                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
+        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
+    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    return out
+
+
+def _relative_base(thr, base, thr_index, K):
+    """Checks the fleet base of a relative attribution: thr, base [., 2] and the optional index."""
+    N.require_device(thr, "thr")
+    if thr.dtype != torch.int32 or thr.dim() != 1 or not thr.is_contiguous():
+        raise ValueError("thr must be a contiguous int32 tensor")
+    _tail_tensor(base, "base", torch.int64, (thr.numel(), 2))
+    if thr_index is None:
+        if thr.numel() != K:
+            raise ValueError("thr must hold K entries (or pass thr_index)")
+    else:
+        _tail_tensor(thr_index, "thr_index", torch.int32, (K,))
+
+
 def histogram_tail_attribution(counts: torch.Tensor, *, top: int, kind: str,
                                thr: Optional[torch.Tensor] = None,
                                thr_index: Optional[torch.Tensor] = None,
@@ -976,38 +923,15 @@ def histogram_tail_attribution(counts: torch.Tensor, *, top: int, kind: str,
     if kind_code == N.NVRX_ATTR_RELATIVE:
         if thr is None or base is None:
             raise ValueError("kind='relative' needs thr and base")
-        N.require_device(thr, "thr")
-        if thr.dtype != torch.int32 or thr.dim() != 1 or not thr.is_contiguous():
-            raise ValueError("thr must be a contiguous int32 tensor")
-        _tail_tensor(base, "base", torch.int64, (thr.numel(), 2))
-        if thr_index is None:
-            if thr.numel() != K:
-                raise ValueError("thr must hold K entries (or pass thr_index)")
-        else:
-            _tail_tensor(thr_index, "thr_index", torch.int32, (K,))
+        _relative_base(thr, base, thr_index, K)
         hist = hist_index = col_valid = None
     else:
         if hist is None or permille is None:
             raise ValueError("kind='individual' needs hist and permille")
         pm = tail_permille(permille)
-        stride = int(hist_stride)
-        if stride < 0 or (stride and hist_index is None and stride < K):
-            raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
-        N.require_device(hist, "hist")
-        if hist.dtype not in (torch.int32, torch.uint32) or hist.data_ptr() % 16:
-            raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
-        _tail_tensor(hist, "hist", hist.dtype, (R, stride or K, N.HIST_BINS))
-        if hist_index is not None:
-            _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
-        _u8_vector(col_valid, "col_valid", K)
+        stride = _history_slots(R, K, hist, hist_stride, hist_index, col_valid, compact=False)
         thr = thr_index = base = None
-    if out is None:
-        out = TailAttribution.empty(R, K, top, d)
-    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
-                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
-                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
-        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
-    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    out = _attribution_outputs(R, K, top, d, out)
     a = N.TailAttrArgs(R, K, counts.data_ptr(), kind_code, top, N.ptr(thr), N.ptr(thr_index),
                        N.ptr(base), N.ptr(hist), stride, N.ptr(hist_index), N.ptr(col_valid), pm,
                        out.idx.data_ptr(), out.loss.data_ptr(), out.tail_ns.data_ptr(),
@@ -1034,22 +958,8 @@ def segment_tail_attribution_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
     top, _ = attribution_request(top, "relative")
     R = _segment_rows(ns, seg_off, seg_len, K)
     d = ns.device
-    N.require_device(thr, "thr")
-    if thr.dtype != torch.int32 or thr.dim() != 1 or not thr.is_contiguous():
-        raise ValueError("thr must be a contiguous int32 tensor")
-    _tail_tensor(base, "base", torch.int64, (thr.numel(), 2))
-    if thr_index is None:
-        if thr.numel() != K:
-            raise ValueError("thr must hold K entries (or pass thr_index)")
-    else:
-        _tail_tensor(thr_index, "thr_index", torch.int32, (K,))
-    if out is None:
-        out = TailAttribution.empty(R, K, top, d)
-    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
-                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
-                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
-        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
-    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    _relative_base(thr, base, thr_index, K)
+    out = _attribution_outputs(R, K, top, d, out)
     a = N.SegTailAttrArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
                           int(aligned16), top, thr.data_ptr(), N.ptr(thr_index), base.data_ptr(),
                           out.idx.data_ptr(), out.loss.data_ptr(), out.tail_ns.data_ptr(),
@@ -1081,23 +991,8 @@ def segment_history_attribution_ragged(ns: torch.Tensor, seg_off: torch.Tensor,
     pm = tail_permille(permille)
     R = _segment_rows(ns, seg_off, seg_len, K)
     d = ns.device
-    stride = int(hist_stride)
-    if stride < 0 or (stride and hist_index is None and stride < K):
-        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
-    N.require_device(hist, "hist")
-    if hist.dtype not in (torch.int32, torch.uint32) or hist.data_ptr() % 16:
-        raise ValueError("hist must be a contiguous, 16-byte aligned int32 tensor")
-    _tail_tensor(hist, "hist", hist.dtype, (R, stride or K, N.HIST_BINS))
-    if hist_index is not None:
-        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
-    _u8_vector(col_valid, "col_valid", K)
-    if out is None:
-        out = TailAttribution.empty(R, K, top, d)
-    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
-                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
-                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
-        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
-    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    stride = _history_slots(R, K, hist, hist_stride, hist_index, col_valid, compact=False)
+    out = _attribution_outputs(R, K, top, d, out)
     a = N.SegHistAttrArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
                           int(aligned16), top, hist.data_ptr(), stride, N.ptr(hist_index),
                           N.ptr(col_valid), pm, out.idx.data_ptr(), out.loss.data_ptr(),
@@ -1128,23 +1023,8 @@ def segment_history_attribution_compact_ragged(ns: torch.Tensor, seg_off: torch.
     pm = tail_permille(permille)
     R = _segment_rows(ns, seg_off, seg_len, K)
     d = ns.device
-    stride = int(hist_stride)
-    if stride < 0 or (stride and hist_index is None and stride < K):
-        raise ValueError("hist_stride must be 0 (= K) or, without hist_index, at least K")
-    N.require_device(chist, "chist")
-    if chist.dtype != torch.uint8 or chist.data_ptr() % 16:
-        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor")
-    _tail_tensor(chist, "chist", torch.uint8, (R, stride or K, N.CHIST_BYTES))
-    if hist_index is not None:
-        _tail_tensor(hist_index, "hist_index", torch.int32, (K,))
-    _u8_vector(col_valid, "col_valid", K)
-    if out is None:
-        out = TailAttribution.empty(R, K, top, d)
-    for name, dt in (("idx", torch.int32), ("loss", torch.float64), ("tail_ns", torch.int64),
-                     ("total_ns", torch.int64), ("tail_calls", torch.int32),
-                     ("thr_bucket", torch.int32), ("base_share", torch.float64)):
-        _tail_tensor(getattr(out, name), "out." + name, dt, (R, top))
-    _tail_tensor(out.loss_all, "out.loss_all", torch.float64, (R, K))
+    stride = _history_slots(R, K, chist, hist_stride, hist_index, col_valid, compact=True)
+    out = _attribution_outputs(R, K, top, d, out)
     a = N.SegCHistAttrArgs(R, K, ns.data_ptr(), seg_off.data_ptr(), N.ptr(seg_len), max_len, cap,
                            int(aligned16), top, chist.data_ptr(), stride, N.ptr(hist_index),
                            N.ptr(col_valid), pm, out.idx.data_ptr(), out.loss.data_ptr(),
