@@ -210,6 +210,116 @@ def _half_life(half_life) -> Optional[int]:
     return int(half_life)
 
 
+class _FleetTailLayout:
+    """The packed results of the fleet's tail scores (``tail_scores``, ``tail_scores_records``), one
+    device-to-host copy per call:
+    [score f64 R][tail_ns i64 R][total_ns i64 R][fleet_sums i64 2][thr i32 K+pad][strag u8 R]"""
+
+    def __init__(self, R: int, K: int):
+        self.R, self.K = R, K
+        self.thr = 8 * (3 * R + 2)                      # the 8-byte fields end, thr begins
+        self.strag = self.thr + 4 * ((K + 1) // 2 * 2)  # (thr padded to 8 bytes)
+        self.nbytes = self.strag + R
+
+    def views(self, buf: torch.Tensor):
+        """(outputs, thr [K], fleet_sums [2]): the device views of a packed buffer."""
+        R = self.R
+        i64 = buf[:self.thr].view(torch.int64)
+        out = ops.TailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
+                             buf[self.strag:self.nbytes])
+        return out, buf[self.thr:self.strag].view(torch.int32)[:self.K], i64[3 * R:]
+
+    def unpack(self, host: np.ndarray, tail_calls, attribution) -> BatchTailScores:
+        """The results in the host copy of a packed buffer."""
+        R = self.R
+        h64 = host[:self.thr].view(np.uint64)
+        ftail, ftotal = int(h64[3 * R]), int(h64[3 * R + 1])
+        return BatchTailScores(h64[:R].view(np.float64).copy(), h64[R:2 * R].copy(),
+                               h64[2 * R:3 * R].copy(),
+                               float(ftail) / float(ftotal) if ftotal else float("nan"),
+                               host[self.strag:self.nbytes].astype(bool),
+                               host[self.thr:self.strag].view(np.int32)[:self.K].copy(),
+                               tail_calls, attribution)
+
+
+class _HistoryTailLayout:
+    """The packed results of the individual tail scores, one device-to-host copy per call
+    (``ops.HistoryTailScores.packed``; ``folded`` with the compact history only):
+    [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns i64 R]([folded i64 R])[strag u8 R]"""
+
+    def __init__(self, R: int, folded: bool):
+        self.R, self.folded = R, folded
+        self.nbytes = 49 * R if folded else 41 * R
+
+    def views(self, buf: torch.Tensor):
+        """(outputs, folded [R] or None): the device views of a packed buffer."""
+        return ops.HistoryTailScores.packed(buf, self.R, self.folded)
+
+    def unpack(self, host: np.ndarray, tail_calls, attribution) -> BatchIndividualTailScores:
+        """The results in the host copy of a packed buffer."""
+        score, tail, total, btail, btotal, strag, folded = ops.HistoryTailScores.unpack(
+            host, self.R, self.folded)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
+        return BatchIndividualTailScores(score, tail, total, share, strag, btail, btotal, tail_calls,
+                                         folded=folded, attribution=attribution)
+
+
+class _CountsSource:
+    """An interval given as histogram counts [R, K, 240], for the tail-score drivers: each
+    operation is the ``ops`` entry that takes counts.  ``_BucketSource`` is its twin."""
+
+    def __init__(self, counts: torch.Tensor):
+        self.counts = counts
+
+    def fleet_histogram(self, out):
+        ops.histogram_sum(self.counts, out=out)
+
+    def fleet_scores(self, thr, sums, **kw):
+        return ops.histogram_tail_scores(self.counts, thr, sums, **kw)
+
+    def fleet_attribution(self, thr, base, **kw):
+        ops.histogram_tail_attribution(self.counts, kind="relative", thr=thr, base=base, **kw)
+
+    def history_scores(self, hist, compact: bool, **kw):
+        """Score against / update the dense history, or the compact one (``folded=`` in kw)."""
+        if compact:
+            return ops.histogram_history_scores_compact(self.counts, hist, **kw)[0]
+        return ops.histogram_history_scores(self.counts, hist, **kw)
+
+    def history_attribution(self, hist, **kw):
+        ops.histogram_tail_attribution(self.counts, kind="individual", hist=hist, **kw)
+
+
+class _BucketSource:
+    """An interval given as the buckets a record-stream call laid out (``records_bucket``: every
+    bucket written out, trimmed to ``cap``, the starts padded to 16 bytes), for the tail-score
+    drivers: each operation is the ragged ``ops`` entry, without the counts."""
+
+    def __init__(self, out_ns, seg_off, seg_len, K: int, max_len: int):
+        self.segs = (out_ns, seg_off, seg_len, K, max_len)
+
+    def fleet_histogram(self, out):
+        ops.segment_fleet_histogram_ragged(*self.segs, aligned16=True, out=out)
+
+    def fleet_scores(self, thr, sums, **kw):
+        return ops.segment_tail_scores_ragged(*self.segs, thr, sums, aligned16=True, **kw)
+
+    def fleet_attribution(self, thr, base, **kw):
+        ops.segment_tail_attribution_ragged(*self.segs, thr, base, aligned16=True, **kw)
+
+    def history_scores(self, hist, compact: bool, **kw):
+        if compact:
+            return ops.segment_history_scores_compact_ragged(*self.segs, hist, aligned16=True, **kw)[0]
+        return ops.segment_history_scores_ragged(*self.segs, hist, aligned16=True, **kw)
+
+    def history_attribution(self, hist, **kw):
+        ops.segment_history_attribution_ragged(*self.segs, hist, aligned16=True, **kw)
+
+    def compact_history_attribution(self, chist, **kw):
+        ops.segment_history_attribution_compact_ragged(*self.segs, chist, aligned16=True, **kw)
+
+
 class MatrixReporter:
     def __init__(self, R: int, K: int, *, cap: int = 8192, relative: bool = True,
                  individual: bool = True, thr_rel: float = 0.75, thr_ind: float = 0.75,
@@ -299,6 +409,18 @@ class MatrixReporter:
         self._column_ref(b)
         return st
 
+    def _bucket_scratch(self, have: Optional[tuple], n: int, pushes: bool) -> tuple:
+        """The record-stream bucketing scratch for ``n`` records -- (seg_off i64, seg_len i32,
+        bucketed ns i32, per-bucket push counts i32 or None) -- ``have`` where it holds them."""
+        need = ops.records_bucket_capacity(n, self.R, self.K)
+        if have is not None and have[2].numel() >= need:
+            return have
+        d, nseg = self.device, self.R * self.K
+        return (torch.empty(nseg, dtype=torch.int64, device=d),
+                torch.empty(nseg, dtype=torch.int32, device=d),
+                torch.empty(max(need, 1), dtype=torch.int32, device=d),
+                torch.empty(nseg, dtype=torch.int32, device=d) if pushes else None)
+
     def compute_stats_records(self, recs: torch.Tensor, rec_off: torch.Tensor,
                               bufs: Optional[_ReportBuffers] = None) -> ops.SegmentStats:
         """recs [n, 2] int32 {slot, ns} of R streams (rec_off [R+1] int64, device): the
@@ -306,13 +428,8 @@ class MatrixReporter:
         b = self.own if bufs is None else bufs
         self._order_after_inflight()
         n = recs.shape[0]
-        need = ops.records_bucket_capacity(n, self.R, self.K)
-        if b.bucket is None or b.bucket[2].numel() < need:
-            d = self.device
-            # (no per-bucket push counts: a report needs the kept records only)
-            b.bucket = (torch.empty(self.R * self.K, dtype=torch.int64, device=d),
-                        torch.empty(self.R * self.K, dtype=torch.int32, device=d),
-                        torch.empty(max(need, 1), dtype=torch.int32, device=d), None)
+        # (no per-bucket push counts: a report needs the kept records only)
+        b.bucket = self._bucket_scratch(b.bucket, n, pushes=False)
         max_len = min(self.cap, n) if self.cap > 0 else n
         b.clean = False
         return ops.records_stats(recs, rec_off, self.K, self.cap, max(max_len, 1), mode=self.mode,
@@ -453,89 +570,102 @@ class MatrixReporter:
         the reference."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "relative")[0] if attribute else 0
-        if self.exchange:
-            raise NotImplementedError("MatrixReporter.tail_scores: tail scores across kernel "
-                                      "shards (exchange=True) are not supported")
-        R, K, d = self.R, self.K, self.device
+        self._refuse_exchange("tail_scores")
+        R, K = self.R, self.K
         if tuple(counts.shape) != (R, K, histograms.BINS):
             raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
         self._order_after_inflight()
         if self._tail is None:
-            # packed: [score f64 R][tail_ns i64 R][total_ns i64 R][fleet_sums i64 2][thr i32 K+pad][strag u8 R]
-            kp = (K + 1) // 2 * 2
-            self._tail = dict(buf=torch.zeros(8 * (3 * R + 2) + 4 * kp + R, dtype=torch.uint8, device=d),
-                              fleet=torch.empty((K, histograms.BINS), dtype=torch.int64, device=d),
-                              calls=None, kp=kp)
-        t = self._tail
-        kp, buf = t["kp"], t["buf"]
-        if top:  # the same layout at the head of a longer buffer
-            aoff = self._tail_attr_buffers(t, buf.numel())
-            if t.get("base") is None:
-                t["base"] = torch.empty((K, 2), dtype=torch.int64, device=d)
-            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
-        base_len = t["buf"].numel()
-        i64 = buf[:8 * (3 * R + 2)].view(torch.int64)
-        thr = buf[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(torch.int32)[:K]
-        sums = i64[3 * R:]
-        out = ops.TailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                             buf[8 * (3 * R + 2) + 4 * kp:base_len])
-        if tail_calls and t["calls"] is None:
-            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
-        ops.histogram_sum(counts, out=t["fleet"])
-        ops.histogram_tail_threshold(t["fleet"], pm, col_valid=self.col_valid, thr=thr, fleet_sums=sums)
-        res = ops.histogram_tail_scores(counts, thr, sums, out=out,
-                                        score_thr=self.thr_rel if threshold is None else threshold,
-                                        tail_calls=t["calls"] if tail_calls else False)
-        if top:
-            ops.histogram_tail_base(t["fleet"], thr, out=t["base"])
-            ops.histogram_tail_attribution(
-                counts, top=top, kind="relative", thr=thr, base=t["base"],
-                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
-        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
-        h64 = host[:8 * (3 * R + 2)].view(np.uint64)
-        ftail, ftotal = int(h64[3 * R]), int(h64[3 * R + 1])
-        return BatchTailScores(h64[:R].view(np.float64).copy(), h64[R:2 * R].copy(),
-                               h64[2 * R:3 * R].copy(),
-                               float(ftail) / float(ftotal) if ftotal else float("nan"),
-                               host[8 * (3 * R + 2) + 4 * kp:base_len].astype(bool),
-                               host[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(np.int32)[:K].copy(),
-                               res.tail_calls,
-                               BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
-                               if top else None)
+            self._tail = self._fleet_tail_work()
+        return self._fleet_tail_scores(self._tail, _CountsSource(counts), pm, threshold, tail_calls, top)
 
-    def _records_tail_work(self, n: int, owner: str) -> dict:
-        """The tail work tensors of the record-stream methods (``tail_scores_records``,
-        ``individual_tail_scores_records``), allocated at first use, the bucketing scratch grown to
-        hold ``n`` records.  ``owner`` names the path that is about to bucket into them:
-        ``compact_tail_attribution`` reads the buckets later and must know they are still the
-        compact call's."""
-        R, K, d = self.R, self.K, self.device
+    def _refuse_exchange(self, method: str) -> None:
+        if self.exchange:
+            raise NotImplementedError(f"MatrixReporter.{method}: tail scores across kernel shards "
+                                      "(exchange=True) are not supported")
+
+    def _tail_work(self, layout, **tensors) -> dict:
+        """The work of one tail-score family: its packed-result layout, buffer (zeroed) and the
+        layout's views of it (made once: every call without ``attribute`` uses them), the
+        ``tail_calls`` matrix (allocated on request) and the family's own tensors."""
+        buf = torch.zeros(layout.nbytes, dtype=torch.uint8, device=self.device)
+        return dict(layout=layout, buf=buf, views=layout.views(buf), calls=None, **tensors)
+
+    def _fleet_tail_work(self, **more) -> dict:
+        """The fleet histogram and packed outputs (``_FleetTailLayout``) of ``tail_scores``; the
+        record-stream methods keep a set of their own."""
+        return self._tail_work(_FleetTailLayout(self.R, self.K), **more,
+                               fleet=torch.empty((self.K, histograms.BINS), dtype=torch.int64,
+                                                 device=self.device))
+
+    def _bucket(self, recs: torch.Tensor, rec_off: torch.Tensor, owner: str, pm: int) -> _BucketSource:
+        """Bucket the record streams into the tail work tensors of the record-stream methods
+        (``_rtail``: what ``tail_scores`` keeps and the bucketing scratch, allocated at first use
+        and grown on demand) and return the buckets as a source.  records_bucket writes every
+        bucket out (records_stats reduces the tiny ones in LDS and marks them seg_len < 0); the
+        windows are already trimmed to ``cap``, their starts padded to 16 bytes.  ``owner`` names
+        the path that buckets: a compact call leaves its buckets and permille for
+        ``compact_tail_attribution``, which must know later that they are still that call's."""
         if self._rtail is None:
-            # packed as tail_scores packs:
-            # [score f64 R][tail_ns i64 R][total_ns i64 R][fleet_sums i64 2][thr i32 K+pad][strag u8 R]
-            kp = (K + 1) // 2 * 2
-            self._rtail = dict(buf=torch.zeros(8 * (3 * R + 2) + 4 * kp + R, dtype=torch.uint8, device=d),
-                               fleet=torch.empty((K, histograms.BINS), dtype=torch.int64, device=d),
-                               calls=None, kp=kp, bucket=None, owner=None)
+            self._rtail = self._fleet_tail_work(bucket=None, owner=None)
         t = self._rtail
         t["owner"] = owner
-        need = ops.records_bucket_capacity(n, R, K)
-        if t["bucket"] is None or t["bucket"][2].numel() < need:
-            t["bucket"] = (torch.empty(R * K, dtype=torch.int64, device=d),
-                           torch.empty(R * K, dtype=torch.int32, device=d),
-                           torch.empty(max(need, 1), dtype=torch.int32, device=d),
-                           torch.empty(R * K, dtype=torch.int32, device=d))
-        return t
+        n = recs.shape[0]
+        t["bucket"] = self._bucket_scratch(t["bucket"], n, pushes=True)
+        seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, self.K, self.cap, out=t["bucket"])
+        src = _BucketSource(out_ns, seg_off, seg_len, self.K,
+                            max(min(self.cap, n) if self.cap > 0 else n, 1))
+        if owner == "compact":
+            t["compact_call"] = (src, pm)
+        return src
 
-    def _history_tail_work(self) -> dict:
-        """The history and packed outputs of the individual tail scores (both methods continue the
-        one history), allocated at first use."""
+    def _tail_call(self, t: dict, top: int, tail_calls: bool):
+        """(buf, views, aoff, calls) of one call on the work ``t``: the packed buffer and the
+        layout's views of it -- with ``top`` the same layout at the head of a longer buffer, the
+        attribution at ``aoff`` -- and what to pass as ``tail_calls=``."""
+        buf, views, aoff = t["buf"], t["views"], None
+        if top:
+            aoff = self._tail_attr_buffers(t, t["layout"].nbytes)
+            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * self.R * top]
+            views = t["layout"].views(buf)
+        if tail_calls and t["calls"] is None:
+            t["calls"] = torch.empty((self.R, self.K), dtype=torch.int32, device=self.device)
+        return buf, views, aoff, t["calls"] if tail_calls else False
+
+    def _tail_land(self, t: dict, buf: torch.Tensor, aoff, top: int, res):
+        """The one device-to-host copy of a tail-score call, then the layout's results."""
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        attribution = (BatchTailAttribution.unpack(host[aoff:], self.R, top, t["loss_all"])
+                       if top else None)
+        return t["layout"].unpack(host, res.tail_calls, attribution)
+
+    def _fleet_tail_scores(self, t: dict, src, pm: int, threshold, tail_calls: bool,
+                           top: int) -> BatchTailScores:
+        """The fleet's tail scores of the interval ``src`` on the work ``t``: fleet histogram ->
+        threshold buckets -> scores -> (fleet base -> attribution) -> one copy."""
+        buf, (out, thr, sums), aoff, calls = self._tail_call(t, top, tail_calls)
+        if top and t.get("base") is None:
+            t["base"] = torch.empty((self.K, 2), dtype=torch.int64, device=self.device)
+        src.fleet_histogram(t["fleet"])
+        ops.histogram_tail_threshold(t["fleet"], pm, col_valid=self.col_valid, thr=thr, fleet_sums=sums)
+        res = src.fleet_scores(thr, sums, out=out,
+                               score_thr=self.thr_rel if threshold is None else threshold,
+                               tail_calls=calls)
+        if top:
+            ops.histogram_tail_base(t["fleet"], thr, out=t["base"])
+            src.fleet_attribution(thr, t["base"], top=top, out=ops.TailAttribution.packed(
+                buf[aoff:], self.R, top, t["loss_all"]))
+        return self._tail_land(t, buf, aoff, top, res)
+
+    def _history_tail_work(self, clear: bool = True) -> dict:
+        """The history and packed outputs (``_HistoryTailLayout``) of the individual tail scores
+        (both methods continue the one history), allocated at first use; ``clear=False`` leaves
+        the history uninitialised for a caller that overwrites it in full."""
         if self._htail is None:
-            R, K, d = self.R, self.K, self.device
-            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns i64 R][strag u8 R]
-            self._htail = dict(buf=torch.zeros(41 * R, dtype=torch.uint8, device=d),
-                               hist=torch.zeros((R, K, histograms.BINS), dtype=torch.int32, device=d),
-                               calls=None)
+            new = torch.zeros if clear else torch.empty
+            self._htail = self._tail_work(
+                _HistoryTailLayout(self.R, folded=False),
+                hist=new((self.R, self.K, histograms.BINS), dtype=torch.int32, device=self.device))
         return self._htail
 
     def tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor, permille: int = 990,
@@ -560,57 +690,12 @@ class MatrixReporter:
         reporter.  Without it ``.attribution`` stays None.  Beyond the reference."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "relative")[0] if attribute else 0
-        if self.exchange:
-            raise NotImplementedError("MatrixReporter.tail_scores_records: tail scores across "
-                                      "kernel shards (exchange=True) are not supported")
-        R, K, d = self.R, self.K, self.device
-        if rec_off.numel() != R + 1:
-            raise ValueError(f"rec_off must hold {R + 1} offsets")
+        self._refuse_exchange("tail_scores_records")
+        if rec_off.numel() != self.R + 1:
+            raise ValueError(f"rec_off must hold {self.R + 1} offsets")
         self._order_after_inflight()
-        t = self._records_tail_work(recs.shape[0], "relative")
-        kp, buf = t["kp"], t["buf"]
-        n = recs.shape[0]
-        base_len = buf.numel()
-        if top:  # the same layout at the head of a longer buffer
-            aoff = self._tail_attr_buffers(t, base_len)
-            if t.get("base") is None:
-                t["base"] = torch.empty((K, 2), dtype=torch.int64, device=d)
-            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
-        i64 = buf[:8 * (3 * R + 2)].view(torch.int64)
-        thr = buf[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(torch.int32)[:K]
-        sums = i64[3 * R:]
-        out = ops.TailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                             buf[8 * (3 * R + 2) + 4 * kp:base_len])
-        if tail_calls and t["calls"] is None:
-            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
-        # records_bucket writes every bucket out (records_stats reduces the tiny ones in LDS and
-        # marks them seg_len < 0); the windows are already trimmed to `cap`, their starts padded
-        # to 16 bytes
-        seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=t["bucket"])
-        max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
-        ops.segment_fleet_histogram_ragged(out_ns, seg_off, seg_len, K, max_len, aligned16=True,
-                                           out=t["fleet"])
-        ops.histogram_tail_threshold(t["fleet"], pm, col_valid=self.col_valid, thr=thr, fleet_sums=sums)
-        res = ops.segment_tail_scores_ragged(
-            out_ns, seg_off, seg_len, K, max_len, thr, sums, aligned16=True, out=out,
-            score_thr=self.thr_rel if threshold is None else threshold,
-            tail_calls=t["calls"] if tail_calls else False)
-        if top:
-            ops.histogram_tail_base(t["fleet"], thr, out=t["base"])
-            ops.segment_tail_attribution_ragged(
-                out_ns, seg_off, seg_len, K, max_len, thr, t["base"], top=top, aligned16=True,
-                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
-        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
-        h64 = host[:8 * (3 * R + 2)].view(np.uint64)
-        ftail, ftotal = int(h64[3 * R]), int(h64[3 * R + 1])
-        return BatchTailScores(h64[:R].view(np.float64).copy(), h64[R:2 * R].copy(),
-                               h64[2 * R:3 * R].copy(),
-                               float(ftail) / float(ftotal) if ftotal else float("nan"),
-                               host[8 * (3 * R + 2) + 4 * kp:base_len].astype(bool),
-                               host[8 * (3 * R + 2):8 * (3 * R + 2) + 4 * kp].view(np.int32)[:K].copy(),
-                               res.tail_calls,
-                               BatchTailAttribution.unpack(host[aoff:], R, top, t["loss_all"])
-                               if top else None)
+        src = self._bucket(recs, rec_off, "relative", pm)
+        return self._fleet_tail_scores(self._rtail, src, pm, threshold, tail_calls, top)
 
     def individual_tail_scores(self, counts: torch.Tensor, permille: int = 990,
                                threshold: Optional[float] = None, absorb: str = "healthy",
@@ -665,6 +750,20 @@ class MatrixReporter:
         tensors, so a pending ``compact_tail_attribution()`` stays valid.  ``history="dense"``
         (default) is the path described above, untouched.  ``convert_tail_history`` moves a
         reporter from one history to the other.  Beyond the reference."""
+        pm, top, half_life = self._individual_request("individual_tail_scores", permille, attribute,
+                                                      absorb, half_life, history)
+        R, K = self.R, self.K
+        if tuple(counts.shape) != (R, K, histograms.BINS):
+            raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
+        self._order_after_inflight()
+        return self._individual_tail_scores(lambda: _CountsSource(counts), history, pm, threshold,
+                                            absorb, tail_calls, top, half_life)
+
+    def _individual_request(self, method: str, permille, attribute, absorb, half_life, history,
+                            instead: str = ""):
+        """The request checks both individual tail-score methods start with, in their order;
+        returns (permille, top, half_life).  ``instead``: what the refusal of ``attribute`` with the
+        compact history points to."""
         pm = ops.tail_permille(permille)
         top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
         if absorb not in ABSORB_MODES:
@@ -672,54 +771,40 @@ class MatrixReporter:
         half_life = _half_life(half_life)
         if history not in ("dense", "compact"):
             raise ValueError(f"history must be 'dense' or 'compact', got {history!r}")
-        if self.exchange:
-            raise NotImplementedError("MatrixReporter.individual_tail_scores: tail scores across "
-                                      "kernel shards (exchange=True) are not supported")
+        self._refuse_exchange(method)
         if history == "compact" and top:
-            raise NotImplementedError("MatrixReporter.individual_tail_scores: attribute= is not "
-                                      "available with the compact history")
-        R, K, d = self.R, self.K, self.device
-        if tuple(counts.shape) != (R, K, histograms.BINS):
-            raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
-        self._order_after_inflight()
-        if history == "compact":
-            return self._individual_tail_scores_compact(counts, pm, threshold, absorb, tail_calls,
-                                                        half_life)
-        t = self._history_tail_work()
-        self._age_before("dense", half_life, absorb)
-        buf = t["buf"]
-        if top:  # the same layout at the head of a longer buffer
-            aoff = self._tail_attr_buffers(t, 41 * R)
-            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
-        i64 = buf[:40 * R].view(torch.int64)
-        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                                    i64[3 * R:4 * R], i64[4 * R:], buf[40 * R:41 * R])
-        if tail_calls and t["calls"] is None:
-            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
-        res = ops.histogram_history_scores(
-            counts, t["hist"], permille=pm, update=absorb == "always" and not top,
-            col_valid=self.col_valid,
-            score_thr=self.thr_ind if threshold is None else threshold,
-            tail_calls=t["calls"] if tail_calls else False, out=out)
-        if top:  # between the score and the update: the history the score saw
-            ops.histogram_tail_attribution(
-                counts, top=top, kind="individual", hist=t["hist"], permille=pm,
-                col_valid=self.col_valid,
-                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
+            raise NotImplementedError(f"MatrixReporter.{method}: attribute= is not available with "
+                                      f"the compact history{instead}")
+        return pm, top, half_life
+
+    def _individual_tail_scores(self, source, history: str, pm: int, threshold, absorb: str,
+                                tail_calls: bool, top: int,
+                                half_life: Optional[int]) -> BatchIndividualTailScores:
+        """The individual tail scores of one interval against the ``history`` ("dense" /
+        "compact") the reporter keeps: age -> score -> (attribution) -> update -> one copy.
+        ``source()`` gives the interval; it is asked after the age pass, so the bucketing it may
+        launch keeps its place.  ``absorb="always"`` is one fused score-and-update launch unless
+        ``top`` puts the attribution between the two, where it sees the history the score saw."""
+        compact = history == "compact"
+        t = self._compact_tail_work() if compact else self._history_tail_work()
+        self._age_before(history, half_life, absorb)
+        src = source()
+        buf, (out, folded), aoff, calls = self._tail_call(t, top, tail_calls)
+        hist = t["chist" if compact else "hist"]
+        kw = dict(permille=pm, col_valid=self.col_valid, **({"folded": folded} if compact else {}))
+        res = src.history_scores(hist, compact, update=absorb == "always" and not top,
+                                 score_thr=self.thr_ind if threshold is None else threshold,
+                                 tail_calls=calls, out=out, **kw)
+        if top:  # (the dense history only: the request checks refuse it with the compact one)
+            src.history_attribution(hist, permille=pm, top=top, col_valid=self.col_valid,
+                                    out=ops.TailAttribution.packed(buf[aoff:], self.R, top,
+                                                                   t["loss_all"]))
         if absorb == "healthy" or (absorb == "always" and top):
-            ops.histogram_history_scores(counts, t["hist"], permille=pm, score=False,
-                                         col_valid=self.col_valid,
-                                         skip_rows=out.strag if absorb == "healthy" else None)
-        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
-        h64 = host[:40 * R].view(np.uint64).reshape(5, R).copy()
-        btail, btotal = h64[3], h64[4]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
-        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
-                                         host[40 * R:41 * R].astype(bool), btail, btotal,
-                                         res.tail_calls,
-                                         attribution=BatchTailAttribution.unpack(
-                                             host[aoff:], R, top, t["loss_all"]) if top else None)
+            src.history_scores(hist, compact, score=False,
+                               skip_rows=out.strag if absorb == "healthy" else None, **kw)
+        elif compact and absorb == "never":
+            folded.zero_()  # no update: nothing folded
+        return self._tail_land(t, buf, aoff, top, res)
 
     def individual_tail_scores_records(self, recs: torch.Tensor, rec_off: torch.Tensor,
                                        permille: int = 990, threshold: Optional[float] = None,
@@ -767,152 +852,26 @@ class MatrixReporter:
         history the entries that reach zero are evicted, so a full element admits new buckets
         again and ``.folded`` returns to 0.  ``None`` (default): no aging and no further launch.
         Beyond the reference."""
-        pm = ops.tail_permille(permille)
-        top = ops.attribution_request(attribute, "individual")[0] if attribute else 0
-        if absorb not in ABSORB_MODES:
-            raise ValueError(f"absorb must be one of {ABSORB_MODES}, got {absorb!r}")
-        half_life = _half_life(half_life)
-        if history not in ("dense", "compact"):
-            raise ValueError(f"history must be 'dense' or 'compact', got {history!r}")
-        if self.exchange:
-            raise NotImplementedError("MatrixReporter.individual_tail_scores_records: tail scores "
-                                      "across kernel shards (exchange=True) are not supported")
-        if history == "compact" and top:
-            raise NotImplementedError("MatrixReporter.individual_tail_scores_records: attribute= "
-                                      "is not available with the compact history; call "
-                                      "compact_tail_attribution() after the scores")
-        R, K, d = self.R, self.K, self.device
-        if rec_off.numel() != R + 1:
-            raise ValueError(f"rec_off must hold {R + 1} offsets")
+        pm, top, half_life = self._individual_request(
+            "individual_tail_scores_records", permille, attribute, absorb, half_life, history,
+            instead="; call compact_tail_attribution() after the scores")
+        if rec_off.numel() != self.R + 1:
+            raise ValueError(f"rec_off must hold {self.R + 1} offsets")
         self._order_after_inflight()
-        n = recs.shape[0]
-        w = self._records_tail_work(n, history)
-        if history == "compact":
-            return self._individual_tail_scores_records_compact(recs, rec_off, w, pm, threshold,
-                                                                absorb, tail_calls, half_life)
-        t = self._history_tail_work()
-        self._age_before("dense", half_life, absorb)
-        buf = t["buf"]
-        if top:  # the same layout at the head of a longer buffer
-            aoff = self._tail_attr_buffers(t, 41 * R)
-            buf = t["abuf"][:aoff + ops.TailAttribution.PACKED * R * top]
-        i64 = buf[:40 * R].view(torch.int64)
-        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                                    i64[3 * R:4 * R], i64[4 * R:], buf[40 * R:41 * R])
-        if tail_calls and t["calls"] is None:
-            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
-        # as tail_scores_records: every bucket written out, trimmed to `cap`, starts padded to 16 bytes
-        seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=w["bucket"])
-        max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
-        res = ops.segment_history_scores_ragged(
-            out_ns, seg_off, seg_len, K, max_len, t["hist"], permille=pm,
-            update=absorb == "always" and not top, aligned16=True, col_valid=self.col_valid,
-            score_thr=self.thr_ind if threshold is None else threshold,
-            tail_calls=t["calls"] if tail_calls else False, out=out)
-        if top:  # between the score and the update: the history the score saw
-            ops.segment_history_attribution_ragged(
-                out_ns, seg_off, seg_len, K, max_len, t["hist"], permille=pm, top=top,
-                aligned16=True, col_valid=self.col_valid,
-                out=ops.TailAttribution.packed(buf[aoff:], R, top, t["loss_all"]))
-        if absorb == "healthy" or (absorb == "always" and top):
-            ops.segment_history_scores_ragged(out_ns, seg_off, seg_len, K, max_len, t["hist"],
-                                              permille=pm, score=False, aligned16=True,
-                                              col_valid=self.col_valid,
-                                              skip_rows=out.strag if absorb == "healthy" else None)
-        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
-        h64 = host[:40 * R].view(np.uint64).reshape(5, R).copy()
-        btail, btotal = h64[3], h64[4]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
-        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
-                                         host[40 * R:41 * R].astype(bool), btail, btotal,
-                                         res.tail_calls,
-                                         attribution=BatchTailAttribution.unpack(
-                                             host[aoff:], R, top, t["loss_all"]) if top else None)
+        return self._individual_tail_scores(lambda: self._bucket(recs, rec_off, history, pm), history,
+                                            pm, threshold, absorb, tail_calls, top, half_life)
 
     def _compact_tail_work(self, clear: bool = True) -> dict:
-        """The compact history and packed outputs of the two compact methods (they continue the
-        one history), allocated at first use; ``clear=False`` leaves the history uninitialised
-        for a caller that overwrites it in full."""
+        """The compact history and packed outputs (``_HistoryTailLayout`` with ``folded``) of the
+        two compact methods (they continue the one history), allocated at first use;
+        ``clear=False`` leaves the history uninitialised for a caller that overwrites it in full."""
         if self._ctail is None:
-            R, K, d = self.R, self.K, self.device
             new = torch.zeros if clear else torch.empty
-            # packed: [score f64 R][tail_ns][total_ns][base_tail_ns][base_total_ns][folded i64 R][strag u8 R]
-            self._ctail = dict(buf=torch.zeros(49 * R, dtype=torch.uint8, device=d),
-                               chist=new((R, K, histograms.CHIST_BYTES), dtype=torch.uint8, device=d),
-                               calls=None)
+            self._ctail = self._tail_work(
+                _HistoryTailLayout(self.R, folded=True),
+                chist=new((self.R, self.K, histograms.CHIST_BYTES), dtype=torch.uint8,
+                          device=self.device))
         return self._ctail
-
-    def _individual_tail_scores_compact(self, counts, pm, threshold, absorb, tail_calls,
-                                        half_life=None) -> BatchIndividualTailScores:
-        """``individual_tail_scores(history="compact")`` after its checks: the launches of the
-        dense path with ``ops.histogram_history_scores_compact`` on the compact history."""
-        R, K, d = self.R, self.K, self.device
-        t = self._compact_tail_work()
-        self._age_before("compact", half_life, absorb)
-        buf = t["buf"]
-        i64 = buf[:48 * R].view(torch.int64)
-        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                                    i64[3 * R:4 * R], i64[4 * R:5 * R], buf[48 * R:])
-        folded = i64[5 * R:]
-        if tail_calls and t["calls"] is None:
-            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
-        res, _ = ops.histogram_history_scores_compact(
-            counts, t["chist"], permille=pm, update=absorb == "always", col_valid=self.col_valid,
-            score_thr=self.thr_ind if threshold is None else threshold,
-            tail_calls=t["calls"] if tail_calls else False, out=out, folded=folded)
-        if absorb == "healthy":
-            ops.histogram_history_scores_compact(counts, t["chist"], permille=pm, score=False,
-                                                 col_valid=self.col_valid, skip_rows=out.strag,
-                                                 folded=folded)
-        elif absorb == "never":
-            folded.zero_()  # no update: nothing folded
-        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
-        h64 = host[:48 * R].view(np.uint64).reshape(6, R).copy()
-        btail, btotal = h64[3], h64[4]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
-        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
-                                         host[48 * R:].astype(bool), btail, btotal,
-                                         res.tail_calls, folded=h64[5])
-
-    def _individual_tail_scores_records_compact(self, recs, rec_off, w, pm, threshold, absorb,
-                                                tail_calls, half_life=None) -> BatchIndividualTailScores:
-        """``individual_tail_scores_records(history="compact")`` after its checks: the launches of
-        the dense path with ``ops.segment_history_scores_compact_ragged`` on the compact history."""
-        R, K, d = self.R, self.K, self.device
-        t = self._compact_tail_work()
-        self._age_before("compact", half_life, absorb)
-        buf = t["buf"]
-        i64 = buf[:48 * R].view(torch.int64)
-        out = ops.HistoryTailScores(i64[:R].view(torch.float64), i64[R:2 * R], i64[2 * R:3 * R],
-                                    i64[3 * R:4 * R], i64[4 * R:5 * R], buf[48 * R:])
-        folded = i64[5 * R:]
-        if tail_calls and t["calls"] is None:
-            t["calls"] = torch.empty((R, K), dtype=torch.int32, device=d)
-        n = recs.shape[0]
-        seg_off, seg_len, out_ns, _ = ops.records_bucket(recs, rec_off, K, self.cap, out=w["bucket"])
-        max_len = max(min(self.cap, n) if self.cap > 0 else n, 1)
-        w["compact_call"] = (seg_off, seg_len, out_ns, max_len, pm)  # for compact_tail_attribution
-        res, _ = ops.segment_history_scores_compact_ragged(
-            out_ns, seg_off, seg_len, K, max_len, t["chist"], permille=pm,
-            update=absorb == "always", aligned16=True, col_valid=self.col_valid,
-            score_thr=self.thr_ind if threshold is None else threshold,
-            tail_calls=t["calls"] if tail_calls else False, out=out, folded=folded)
-        if absorb == "healthy":
-            ops.segment_history_scores_compact_ragged(
-                out_ns, seg_off, seg_len, K, max_len, t["chist"], permille=pm, score=False,
-                aligned16=True, col_valid=self.col_valid, skip_rows=out.strag, folded=folded)
-        elif absorb == "never":
-            folded.zero_()  # no update: nothing folded
-        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
-        h64 = host[:48 * R].view(np.uint64).reshape(6, R).copy()
-        btail, btotal = h64[3], h64[4]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            share = np.where(btotal != 0, btail.astype(np.float64) / btotal.astype(np.float64), np.nan)
-        return BatchIndividualTailScores(h64[0].view(np.float64), h64[1], h64[2], share,
-                                         host[48 * R:].astype(bool), btail, btotal,
-                                         res.tail_calls, folded=h64[5])
 
     def compact_tail_history(self) -> Optional[torch.Tensor]:
         """The compact history of ``individual_tail_scores_records(history="compact")`` (uint8
@@ -941,9 +900,7 @@ class MatrixReporter:
         or if another record-stream method has re-used the bucketing work tensors since.  Beyond
         the reference."""
         top, _ = ops.attribution_request(top, "individual")
-        if self.exchange:
-            raise NotImplementedError("MatrixReporter.compact_tail_attribution: tail scores across "
-                                      "kernel shards (exchange=True) are not supported")
+        self._refuse_exchange("compact_tail_attribution")
         w, t = self._rtail, self._ctail
         if t is None or w is None or w.get("compact_call") is None:
             raise RuntimeError("MatrixReporter.compact_tail_attribution: no "
@@ -951,16 +908,16 @@ class MatrixReporter:
         if w["owner"] != "compact":
             raise RuntimeError("MatrixReporter.compact_tail_attribution: another record-stream "
                                "method has re-used the buckets of the last compact call")
-        seg_off, seg_len, out_ns, max_len, pm = w["compact_call"]
+        src, pm = w["compact_call"]
         if permille is not None:
             pm = ops.tail_permille(permille)
-        R, K = self.R, self.K
+        R = self.R
         self._order_after_inflight()
         aoff = self._tail_attr_buffers(t, 0)
         buf = t["abuf"][aoff:aoff + ops.TailAttribution.PACKED * R * top]
-        ops.segment_history_attribution_compact_ragged(
-            out_ns, seg_off, seg_len, K, max_len, t["chist"], permille=pm, top=top, aligned16=True,
-            col_valid=self.col_valid, out=ops.TailAttribution.packed(buf, R, top, t["loss_all"]))
+        src.compact_history_attribution(
+            t["chist"], permille=pm, top=top, col_valid=self.col_valid,
+            out=ops.TailAttribution.packed(buf, R, top, t["loss_all"]))
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
         return BatchTailAttribution.unpack(host, R, top, t["loss_all"])
 
@@ -981,28 +938,21 @@ class MatrixReporter:
         reference."""
         if to not in ("compact", "dense"):
             raise ValueError(f"to must be 'compact' or 'dense', got {to!r}")
-        if self.exchange:
-            raise NotImplementedError("MatrixReporter.convert_tail_history: tail scores across "
-                                      "kernel shards (exchange=True) are not supported")
+        self._refuse_exchange("convert_tail_history")
         src = self._htail if to == "compact" else self._ctail
         if src is None:
             raise RuntimeError(f"MatrixReporter.convert_tail_history: no "
                                f"{'dense' if to == 'compact' else 'compact'} history to convert")
         self._order_after_inflight()
-        if to == "compact":
+        if to == "compact":  # (the target uninitialised: either conversion writes all of it)
             t = self._compact_tail_work(clear=False)
-            folded = t["buf"][40 * self.R:48 * self.R].view(torch.int64)
+            folded = t["views"][1]
             ops.compact_history_from_dense(src["hist"], out=t["chist"], folded=folded)
             host = folded.cpu().numpy().view(np.uint64).copy()  # the one device-to-host transfer
             self._htail = None
             self._absorbed = {"dense": 0, "compact": self._absorbed["dense"]}
             return host
-        if self._htail is None:  # allocated uninitialised: the conversion writes every bin
-            R, K, d = self.R, self.K, self.device
-            self._htail = dict(buf=torch.zeros(41 * R, dtype=torch.uint8, device=d),
-                               hist=torch.empty((R, K, histograms.BINS), dtype=torch.int32, device=d),
-                               calls=None)
-        ops.compact_history_to_dense(src["chist"], out=self._htail["hist"])
+        ops.compact_history_to_dense(src["chist"], out=self._history_tail_work(clear=False)["hist"])
         self._ctail = None
         self._absorbed = {"dense": self._absorbed["compact"], "compact": 0}
         return None
@@ -1048,9 +998,7 @@ class MatrixReporter:
         s = ops.age_shift(shift)
         if history not in HISTORY_KINDS:
             raise ValueError(f"history must be one of {HISTORY_KINDS}, got {history!r}")
-        if self.exchange:
-            raise NotImplementedError("MatrixReporter.age_tail_history: tail scores across kernel "
-                                      "shards (exchange=True) are not supported")
+        self._refuse_exchange("age_tail_history")
         dense = self._htail if history in ("dense", "both") else None
         compact = self._ctail if history in ("compact", "both") else None
         if dense is None and compact is None:

@@ -484,6 +484,26 @@ class HistoryTailScores:
         return cls(torch.empty(R, dtype=torch.float64, device=device), i(), i(), i(), i(),
                    torch.empty(R, dtype=torch.uint8, device=device))
 
+    @classmethod
+    def packed(cls, buf: torch.Tensor, R: int, folded: bool = False):
+        """Views of the outputs at the head of one 8-byte aligned uint8 buffer, so that one copy
+        moves them all: [score][tail_ns][total_ns][base_tail_ns][base_total_ns]([folded]) of 8 R
+        bytes each, then strag -- 41 R bytes, 49 R with the ``folded`` counts of the compact
+        entries.  Returns (outputs, the int64 [R] folded view or None); ``unpack`` reads it back."""
+        n = 6 if folded else 5
+        q = buf[:8 * n * R].view(torch.int64).view(n, R)
+        return (cls(q[0].view(torch.float64), q[1], q[2], q[3], q[4], buf[8 * n * R:(8 * n + 1) * R]),
+                q[5] if folded else None)
+
+    @staticmethod
+    def unpack(host: np.ndarray, R: int, folded: bool = False):
+        """The host copy of a ``packed`` buffer as numpy arrays [R]: (score f64, tail_ns,
+        total_ns, base_tail_ns, base_total_ns u64, strag bool, folded u64 or None)."""
+        n = 6 if folded else 5
+        q = host[:8 * n * R].view(np.uint64).reshape(n, R).copy()
+        return (q[0].view(np.float64), q[1], q[2], q[3], q[4],
+                host[8 * n * R:(8 * n + 1) * R].astype(bool), q[5] if folded else None)
+
 
 def _u8_vector(t, name, n):
     if t is not None:
