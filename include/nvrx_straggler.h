@@ -36,7 +36,8 @@
  * nvrx_segment_history_scores_ragged, nvrx_segment_history_attribution_ragged,
  * nvrx_segment_history_scores_compact_ragged, nvrx_segment_history_attribution_compact_ragged,
  * nvrx_compact_history_age, nvrx_histogram_history_age, nvrx_histogram_history_scores_compact,
- * nvrx_compact_history_from_dense, nvrx_compact_history_to_dense.
+ * nvrx_compact_history_from_dense, nvrx_compact_history_to_dense,
+ * nvrx_histogram_history_attribution_compact.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -846,6 +847,52 @@ int nvrx_compact_history_from_dense(const uint32_t* hist, void* chist, int64_t R
                                     uint64_t* folded, void* stream);
 int nvrx_compact_history_to_dense(const void* chist, uint32_t* hist, int64_t R, int64_t stride,
                                   void* stream);
+
+/* The individual tail score attribution of [R][K][240] counts against the COMPACT history: what
+ * nvrx_histogram_tail_attribution(kind = NVRX_ATTR_INDIVIDUAL) is to the dense history, and the
+ * fourth corner of the attributions over {counts, record streams} x {dense, compact history}.  No
+ * reference counterpart.  It adds no definition.  nvrx_histchistattr_args has counts and top, then
+ * `const void* chist` ([R][hist_stride] elements of NVRX_CHIST_BYTES, "Element layout" above, read
+ * only) with hist_stride in elements, hist_index, col_valid and permille, then the eight outputs
+ * of nvrx_tailattr_args with the same meaning.  By definition
+ *   nvrx_histogram_history_attribution_compact  writes into idx, loss, tail_ns, total_ns,
+ *     tail_calls, thr_bucket, base_share ([R][top]) and loss_all ([R][K], written in full) what is
+ *     equal, bit for bit, to what nvrx_histogram_tail_attribution writes with kind =
+ *     NVRX_ATTR_INDIVIDUAL, hist the dense expansion of chist (H[bucket[i]] = count[i] for i < n,
+ *     zero elsewhere) and the same counts, hist_index, col_valid, permille and top: an element
+ *     (r, k) is taken iff col_valid[k] != 0, its slot s >= 0, the element's N = sum of count > 0,
+ *     sum_b C[r][k][b] > 0 and its loss is not NaN.
+ * On the counts nvrx_segment_histogram_ragged writes for the same segments it equals
+ * nvrx_segment_history_attribution_compact_ragged.  Canonical input is assumed.  chist is READ
+ * ONLY here, and the content of the slots no column uses never influences an output: between a
+ * SCORE call and an UPDATE call of nvrx_histogram_history_scores_compact the entry sees the history
+ * the score saw.  A column that is not valid or has no slot is not read, neither its element nor
+ * its counts.
+ * counts and chist 16-byte aligned; the f64 and u64 outputs 8-byte aligned; top in
+ * 1..NVRX_MAX_ATTRIBUTION; permille in 0..1000; hist_stride 0 or, without hist_index, at least K;
+ * K * 240 and R * K below 2^31.  R == 0 or K == 0 launches nothing (outputs untouched).
+ * Stream-ordered: two kernels on `stream` only (every (r, k) has one owner): no allocation, no
+ * synchronisation, no host read-back, no scratch, no atomics, no clear; capturable as a linear
+ * chain with the calls around it. */
+typedef struct nvrx_histchistattr_args {
+    int64_t R, K;
+    const uint32_t* counts;     /* [R][K][NVRX_HIST_BINS] */
+    int32_t top;                /* 1..NVRX_MAX_ATTRIBUTION */
+    const void* chist;          /* [R][hist_stride] elements of NVRX_CHIST_BYTES, read only */
+    int64_t hist_stride;        /* in elements; 0: K */
+    const int32_t* hist_index;  /* [K] or NULL */
+    const uint8_t* col_valid;   /* [K] or NULL */
+    int32_t permille;
+    int32_t* idx;               /* [R][top] */
+    double* loss;               /* [R][top] */
+    uint64_t* tail_ns;          /* [R][top] */
+    uint64_t* total_ns;         /* [R][top] */
+    uint32_t* tail_calls;       /* [R][top] */
+    int32_t* thr_bucket;        /* [R][top] */
+    double* base_share;         /* [R][top] */
+    double* loss_all;           /* [R][K] */
+} nvrx_histchistattr_args;
+int nvrx_histogram_history_attribution_compact(const nvrx_histchistattr_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

@@ -661,6 +661,25 @@ int nvrx_histogram_history_scores_compact(const nvrx_histchist_args* a, void* st
     return hip_status(nvrx::histogram_history_scores_compact(b, S(stream)), fn.c_str());
 }
 
+// the attribution of counts against the compact history (histogram_history_compact_attribution.hip):
+// the checks of the individual kind of nvrx_histogram_tail_attribution, with chist for hist
+int nvrx_histogram_history_attribution_compact(const nvrx_histchistattr_args* a, void* stream) {
+    const std::string fn("nvrx_histogram_history_attribution_compact");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_attribution_top(fn, a)) return rc;
+    if (int rc = check_tail_shape(fn.c_str(), a->R, a->K)) return rc;
+    if (int rc = check_history_slots(fn, a)) return rc;
+    if (a->R > 0 && a->K > 0) {
+        NVRX_CHECK_ARG(a->counts, fn + ": null counts");
+        NVRX_CHECK_ARG(a->chist, fn + ": null chist");
+        if (int rc = check_attribution_outputs_set(fn, a)) return rc;
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->counts & 15) == 0, fn + ": counts not 16-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->chist & 15) == 0, fn + ": chist not 16-byte aligned");
+    if (int rc = check_attribution_outputs_aligned(fn, a)) return rc;
+    return hip_status(nvrx::histogram_history_attribution_compact(*a, S(stream)), fn.c_str());
+}
+
 // the conversion between the two histories (histogram_history_compact.hip): slots, not columns
 static int check_convert(const std::string& fn, const void* hist, const void* chist, int64_t R,
                          int64_t stride) {

@@ -73,6 +73,9 @@ hipError_t segment_history_attribution_compact_ragged(const nvrx_segchistattr_ar
 // individual tail scores from [R][K][240] counts against the compact history, and the conversion
 // between the dense and the compact history (histogram_history_compact.hip)
 hipError_t histogram_history_scores_compact(const nvrx_histchist_args& a, hipStream_t st);
+// the individual tail score attribution of counts against the compact history
+// (histogram_history_compact_attribution.hip)
+hipError_t histogram_history_attribution_compact(const nvrx_histchistattr_args& a, hipStream_t st);
 hipError_t compact_history_from_dense(const uint32_t* hist, void* chist, int64_t R, int64_t stride,
                                       uint64_t* folded, hipStream_t st);
 hipError_t compact_history_to_dense(const void* chist, uint32_t* hist, int64_t R, int64_t stride,

@@ -1,9 +1,10 @@
 // topk_select.h -- what the two top-k kernels share (attribution.hip: the kernels behind a GPU
 // score; histogram_attribution.hip: the kernels behind a tail score): an order-preserving 64-bit
 // key of an f64 loss, the per-thread sorted candidate list in registers (insert / pop), and the
-// wave argmax over (key, column) on DPP.  For the four tail attributions (histogram_attribution,
-// segment_tail_attribution, segment_history_attribution, segment_history_compact_attribution) also
-// the select's first half (NVRX_TOPK_WINNERS), the winner's stores and the host's choice of TOP.
+// wave argmax over (key, column) on DPP.  For the five tail attributions (histogram_attribution,
+// segment_tail_attribution, segment_history_attribution, segment_history_compact_attribution,
+// histogram_history_compact_attribution) also the select's first half (NVRX_TOPK_WINNERS), the
+// winner's stores and the host's choice of TOP.
 #pragma once
 #include <type_traits>
 

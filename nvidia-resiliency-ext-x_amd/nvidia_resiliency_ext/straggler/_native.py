@@ -169,6 +169,15 @@ class SegCHistAttrArgs(ctypes.Structure):
     ]
 
 
+class HistCHistAttrArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("counts", P), ("top", i32), ("chist", P), ("hist_stride", i64),
+        ("hist_index", P), ("col_valid", P), ("permille", i32),
+        ("idx", P), ("loss", P), ("tail_ns", P), ("total_ns", P), ("tail_calls", P),
+        ("thr_bucket", P), ("base_share", P), ("loss_all", P),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -227,6 +236,8 @@ SIGNATURES = {
     "nvrx_compact_history_age": (ctypes.c_int, [P, i64, i64, i32, P, P, P]),
     "nvrx_histogram_history_age": (ctypes.c_int, [P, i64, i64, i32, P]),
     "nvrx_histogram_history_scores_compact": (ctypes.c_int, [ctypes.POINTER(HistCHistArgs), P]),
+    "nvrx_histogram_history_attribution_compact": (ctypes.c_int,
+                                                   [ctypes.POINTER(HistCHistAttrArgs), P]),
     "nvrx_compact_history_from_dense": (ctypes.c_int, [P, P, i64, i64, P, P]),
     "nvrx_compact_history_to_dense": (ctypes.c_int, [P, P, i64, i64, P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),

@@ -290,6 +290,9 @@ class _CountsSource:
     def history_attribution(self, hist, **kw):
         ops.histogram_tail_attribution(self.counts, kind="individual", hist=hist, **kw)
 
+    def compact_history_attribution(self, chist, **kw):
+        ops.histogram_history_attribution_compact(self.counts, chist, **kw)
+
 
 class _BucketSource:
     """An interval given as the buckets a record-stream call laid out (``records_bucket``: every
@@ -745,19 +748,25 @@ class MatrixReporter:
         counted on the compact history.  ``.folded`` (u64 [R], in the same device-to-host copy)
         counts the samples folded in this call; while it stays 0 every result equals
         ``history="dense"``'s bit for bit (``histograms.compact_history_scores`` on the host).
-        ``attribute`` is not taken together with the compact history (NotImplementedError): no
-        device entry attributes counts against it.  The call does not touch the bucketing work
-        tensors, so a pending ``compact_tail_attribution()`` stays valid.  ``history="dense"``
+        ``attribute`` is not taken together with the compact history (NotImplementedError): ask
+        ``compact_tail_attribution(counts=counts)`` after this call, which explains the counts
+        against the compact history on request (``ops.histogram_history_attribution_compact``).
+        The call does not touch the bucketing work tensors, so a pending
+        ``compact_tail_attribution()`` stays valid.  ``history="dense"``
         (default) is the path described above, untouched.  ``convert_tail_history`` moves a
         reporter from one history to the other.  Beyond the reference."""
-        pm, top, half_life = self._individual_request("individual_tail_scores", permille, attribute,
-                                                      absorb, half_life, history)
+        pm, top, half_life = self._individual_request(
+            "individual_tail_scores", permille, attribute, absorb, half_life, history,
+            instead="; call compact_tail_attribution(counts=...) after the scores")
         R, K = self.R, self.K
         if tuple(counts.shape) != (R, K, histograms.BINS):
             raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
         self._order_after_inflight()
-        return self._individual_tail_scores(lambda: _CountsSource(counts), history, pm, threshold,
-                                            absorb, tail_calls, top, half_life)
+        res = self._individual_tail_scores(lambda: _CountsSource(counts), history, pm, threshold,
+                                           absorb, tail_calls, top, half_life)
+        if history == "compact":
+            self._ctail["counts_permille"] = pm  # what compact_tail_attribution(counts=) defaults to
+        return res
 
     def _individual_request(self, method: str, permille, attribute, absorb, half_life, history,
                             instead: str = ""):
@@ -879,8 +888,8 @@ class MatrixReporter:
         before its first use."""
         return None if self._ctail is None else self._ctail["chist"]
 
-    def compact_tail_attribution(self, top: int = 8, *,
-                                 permille: Optional[int] = None) -> BatchTailAttribution:
+    def compact_tail_attribution(self, top: int = 8, *, permille: Optional[int] = None,
+                                 counts: Optional[torch.Tensor] = None) -> BatchTailAttribution:
         """The kernels behind the individual tail scores against the compact history, on request
         (as ``attribute()`` explains the last report): per rank the `top` (1..16) kernels with the
         largest excess tail time ``tail - total * history_share_k`` in ns, for the buckets the
@@ -897,10 +906,23 @@ class MatrixReporter:
         does not bucket again, touches no report buffer and leaves the history bit-identical; it
         queues behind reports in flight, and the results come in one device-to-host copy
         (``loss_all`` stays on the device).  RuntimeError if no compact record-stream call has run,
-        or if another record-stream method has re-used the bucketing work tensors since.  Beyond
-        the reference."""
+        or if another record-stream method has re-used the bucketing work tensors since.
+        ``counts=`` (int32 device tensor [R, K, 240], the histograms ``histograms()`` returned)
+        explains THOSE counts in place of the last record-stream call's buckets, against the
+        compact history as it stands (``ops.histogram_history_attribution_compact``;
+        ``histograms.compact_history_attribution`` on the host): the way to name the kernels behind
+        ``individual_tail_scores(counts, history="compact")``, equal bit for bit to
+        ``individual_tail_scores(counts, attribute=top)`` against the dense history for every rank
+        that call did not absorb, while nothing was folded.  It neither needs nor touches the
+        bucketing work tensors, so a pending record-stream ``compact_tail_attribution()`` stays
+        valid across it.  ``permille=None`` then means the permille of the reporter's last
+        ``individual_tail_scores(history="compact")`` call.  ValueError for a wrong shape;
+        RuntimeError if the reporter has no compact history yet, or if ``permille`` is None and no
+        such call has run.  Beyond the reference."""
         top, _ = ops.attribution_request(top, "individual")
         self._refuse_exchange("compact_tail_attribution")
+        if counts is not None:
+            return self._compact_counts_attribution(counts, top, permille)
         w, t = self._rtail, self._ctail
         if t is None or w is None or w.get("compact_call") is None:
             raise RuntimeError("MatrixReporter.compact_tail_attribution: no "
@@ -916,6 +938,30 @@ class MatrixReporter:
         aoff = self._tail_attr_buffers(t, 0)
         buf = t["abuf"][aoff:aoff + ops.TailAttribution.PACKED * R * top]
         src.compact_history_attribution(
+            t["chist"], permille=pm, top=top, col_valid=self.col_valid,
+            out=ops.TailAttribution.packed(buf, R, top, t["loss_all"]))
+        host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        return BatchTailAttribution.unpack(host, R, top, t["loss_all"])
+
+    def _compact_counts_attribution(self, counts: torch.Tensor, top: int,
+                                    permille: Optional[int]) -> BatchTailAttribution:
+        """``compact_tail_attribution(counts=)``: shape check -> the compact history must exist ->
+        behind the reports in flight -> the entry into the packed buffer -> one copy."""
+        R, K = self.R, self.K
+        if tuple(counts.shape) != (R, K, histograms.BINS):
+            raise ValueError(f"counts must have shape [{R}, {K}, {histograms.BINS}]")
+        t = self._ctail
+        if t is None:
+            raise RuntimeError("MatrixReporter.compact_tail_attribution: the reporter has no "
+                               "compact history to explain the counts against")
+        pm = t.get("counts_permille") if permille is None else ops.tail_permille(permille)
+        if pm is None:
+            raise RuntimeError("MatrixReporter.compact_tail_attribution: permille=None and no "
+                               "individual_tail_scores(history=\"compact\") call to take it from")
+        self._order_after_inflight()
+        aoff = self._tail_attr_buffers(t, 0)
+        buf = t["abuf"][aoff:aoff + ops.TailAttribution.PACKED * R * top]
+        _CountsSource(counts).compact_history_attribution(
             t["chist"], permille=pm, top=top, col_valid=self.col_valid,
             out=ops.TailAttribution.packed(buf, R, top, t["loss_all"]))
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)

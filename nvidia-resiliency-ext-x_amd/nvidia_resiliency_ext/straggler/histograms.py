@@ -723,7 +723,9 @@ def compact_history_attribution(counts, chist, permille: int, top: int, hist_ind
     N their counts' sum, T the bucket of the first entry whose running count passes the rank
     ``(permille * (N - 1)) // 1000``, the base sums ``count * weight`` over the entries / those
     above T.  The content of slots no column uses is not looked at.  Python integers: the host
-    twin of ``ops.segment_history_attribution_compact_ragged``."""
+    twin of ``ops.histogram_history_attribution_compact`` (and of
+    ``MatrixReporter.compact_tail_attribution(counts=)``) on the counts themselves, and through
+    ``segment_compact_history_attribution`` of ``ops.segment_history_attribution_compact_ragged``."""
     pm = _check_permille(permille)
     c, ch = merge(counts), _chist_array(chist)
     if c.ndim != 3 or c.shape[2] != BINS:

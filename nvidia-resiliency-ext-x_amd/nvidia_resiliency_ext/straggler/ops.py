@@ -1055,6 +1055,40 @@ def segment_history_attribution_compact_ragged(ns: torch.Tensor, seg_off: torch.
     return out
 
 
+def histogram_history_attribution_compact(counts: torch.Tensor, chist: torch.Tensor, *,
+                                          permille: int, top: int,
+                                          hist_index: Optional[torch.Tensor] = None,
+                                          hist_stride: int = 0,
+                                          col_valid: Optional[torch.Tensor] = None,
+                                          out: Optional[TailAttribution] = None,
+                                          stream=None) -> TailAttribution:
+    """``histogram_tail_attribution(kind="individual")`` against a compact history ``chist``
+    (uint8 [R, hist_stride or K, 64], read only; the layout of
+    ``histogram_history_scores_compact``): every output equals, bit for bit, that entry's on the
+    dense expansion of ``chist`` (``histograms.compact_to_dense``) -- without the 960 bytes per
+    element (``histograms.compact_history_attribution`` on the host).  Between the score and the
+    update call of ``histogram_history_scores_compact`` this sees the history the score saw.
+    ``counts``, ``hist_index``, ``hist_stride``, ``col_valid``, ``permille``, ``top`` and ``out``
+    as in ``histogram_tail_attribution``.  Two launches, no scratch; ``out.loss_all`` is also the
+    workspace."""
+    top, _ = attribution_request(top, "individual")
+    pm = tail_permille(permille)
+    R, K = _tail_counts(counts)
+    N.require_device(chist, "chist")
+    if chist.dtype != torch.uint8 or chist.dim() != 3 or chist.shape[2] != N.CHIST_BYTES:
+        raise ValueError("chist must be a contiguous, 16-byte aligned uint8 tensor of shape "
+                         "[R, S, 64] (a dense history goes to histogram_tail_attribution)")
+    stride = _history_slots(R, K, chist, hist_stride, hist_index, col_valid, compact=True)
+    out = _attribution_outputs(R, K, top, counts.device, out)
+    a = N.HistCHistAttrArgs(R, K, counts.data_ptr(), top, chist.data_ptr(), stride,
+                            N.ptr(hist_index), N.ptr(col_valid), pm, out.idx.data_ptr(),
+                            out.loss.data_ptr(), out.tail_ns.data_ptr(), out.total_ns.data_ptr(),
+                            out.tail_calls.data_ptr(), out.thr_bucket.data_ptr(),
+                            out.base_share.data_ptr(), out.loss_all.data_ptr())
+    N.call("nvrx_histogram_history_attribution_compact", ctypes.byref(a), _stream(stream))
+    return out
+
+
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,
                scratch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """ref[k] = min_r med[r, k] if every row has k (num > 0), else NaN (reporting.py:255-296)."""
