@@ -37,7 +37,7 @@
  * nvrx_segment_history_scores_compact_ragged, nvrx_segment_history_attribution_compact_ragged,
  * nvrx_compact_history_age, nvrx_histogram_history_age, nvrx_histogram_history_scores_compact,
  * nvrx_compact_history_from_dense, nvrx_compact_history_to_dense,
- * nvrx_histogram_history_attribution_compact.
+ * nvrx_histogram_history_attribution_compact, nvrx_rank_attribution / _plan.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -893,6 +893,54 @@ typedef struct nvrx_histchistattr_args {
     double* loss_all;           /* [R][K] */
 } nvrx_histchistattr_args;
 int nvrx_histogram_history_attribution_compact(const nvrx_histchistattr_args* args, void* stream);
+
+/* Rank attribution: the ranks behind a kernel's tail loss.  No reference counterpart.  The tail
+ * attributions above name, per row, the kernels that cost a rank its score, and leave loss_all[R][K]
+ * on the device.  This reads such a matrix column-wise: per kernel, the `top` ranks that lose the
+ * most time on it, and how many lose any.  The definition is part of the ABI.
+ * Input:  loss       f64 [R][ld], row-major, ld >= K (0: K), 8-byte aligned
+ *         row_valid  u8 [R] or NULL: a row with row_valid[r] == 0 counts as not taken for every
+ *                    column (the `strag` output of a score call, passed straight in)
+ *         top        1..NVRX_MAX_ATTRIBUTION
+ * An element (r, k) is TAKEN iff its row is valid and loss[r][k] is not NaN.  Outputs, per column k:
+ *     idx[k][j]       i32 [K][top]: the row of the j-th largest taken loss.  Ties go to the lower
+ *                     row; -0.0 and +0.0 tie; +-inf and negative losses order like any value; -1
+ *                     beyond the taken elements
+ *     loss_out[k][j]  f64 [K][top]: that element's bits as they stand in the input (re-read, never
+ *                     rebuilt from a sort key: -0.0 stays -0.0); NaN where idx = -1
+ *     taken[k]        i32: the number of taken elements
+ *     positive[k]     i32: the number of taken elements with loss > 0.0 (the ranks that lost time
+ *                     on the kernel at all)
+ * No f64 column sums: they would depend on the order of the additions.
+ * nvrx_rank_attribution_plan: pure host function, the launch plan of a shape: tiles (workgroups
+ *   along K, 64 columns each), splits (>= 1: workgroups along R; 1 means one kernel that writes the
+ *   outputs, more a second kernel that merges the splits' partial lists) and work_bytes (0 with one
+ *   split).  work_bytes does not decrease as R or top grow with the other two fixed.  R == 0 or
+ *   K == 0: tiles 0, splits 1, work_bytes 0.  Any output pointer may be NULL.  Negative R or K or a
+ *   top out of range is an error.
+ * nvrx_rank_attribution: `work` is device memory of at least work_bytes, 8-byte aligned (may be
+ *   NULL when work_bytes is 0); its content is unspecified afterwards.  R * ld below 2^31.  R == 0
+ *   or K == 0 launches nothing and leaves the outputs untouched.  A top out of range, ld below K, a
+ *   missing loss or output, a missing work where the plan needs one, or a misaligned loss, loss_out
+ *   or work is an error.  Stream-ordered: one or two kernels on `stream` only (every (column,
+ *   split) has one owner): no allocation, no synchronisation, no host read-back, no atomics, no
+ *   clear, no scratch; capturable as a linear chain with the calls around it.  Two calls on the
+ *   same input write the same bytes. */
+typedef struct nvrx_rankattr_args {
+    int64_t R, K;
+    const double* loss;         /* [R][ld] */
+    int64_t ld;                 /* row stride in elements; 0: K */
+    const uint8_t* row_valid;   /* [R] or NULL */
+    int32_t top;                /* 1..NVRX_MAX_ATTRIBUTION */
+    int32_t* idx;               /* [K][top] */
+    double* loss_out;           /* [K][top] */
+    int32_t* taken;             /* [K] */
+    int32_t* positive;          /* [K] */
+    void* work;                 /* work_bytes of nvrx_rank_attribution_plan, or NULL when 0 */
+} nvrx_rankattr_args;
+int nvrx_rank_attribution_plan(int64_t R, int64_t K, int32_t top, int64_t* tiles, int64_t* splits,
+                               int64_t* work_bytes);
+int nvrx_rank_attribution(const nvrx_rankattr_args* args, void* stream);
 
 /* ---------------------------------------------------------------- scoring */
 /* ref[k] = min over r of med[r][k] if num[r][k] > 0 for every r, else NaN.

@@ -680,6 +680,46 @@ int nvrx_histogram_history_attribution_compact(const nvrx_histchistattr_args* a,
     return hip_status(nvrx::histogram_history_attribution_compact(*a, S(stream)), fn.c_str());
 }
 
+// the ranks behind a kernel's tail loss (rank_attribution.hip): the plan is pure host code
+static int check_rank_request(const std::string& fn, int64_t R, int64_t K, int32_t top) {
+    NVRX_CHECK_ARG(R >= 0, fn + ": negative R");
+    NVRX_CHECK_ARG(K >= 0, fn + ": negative K");
+    NVRX_CHECK_ARG(top >= 1 && top <= NVRX_MAX_ATTRIBUTION,
+                   fn + ": top must be in [1, NVRX_MAX_ATTRIBUTION = 16]");
+    return NVRX_OK;
+}
+
+int nvrx_rank_attribution_plan(int64_t R, int64_t K, int32_t top, int64_t* tiles, int64_t* splits,
+                               int64_t* work_bytes) {
+    if (int rc = check_rank_request("nvrx_rank_attribution_plan", R, K, top)) return rc;
+    nvrx::rank_attribution_plan(R, K, top, tiles, splits, work_bytes);
+    return NVRX_OK;
+}
+
+int nvrx_rank_attribution(const nvrx_rankattr_args* a, void* stream) {
+    const std::string fn("nvrx_rank_attribution");
+    const int64_t lim = ((int64_t)1 << 31) - 1;
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_rank_request(fn, a->R, a->K, a->top)) return rc;
+    NVRX_CHECK_ARG(a->ld == 0 || a->ld >= a->K, fn + ": ld below K");
+    const int64_t ld = a->ld ? a->ld : a->K;
+    NVRX_CHECK_ARG(a->R == 0 || ld <= lim / a->R, fn + ": R * ld must be below 2^31");
+    if (a->R > 0 && a->K > 0) {
+        int64_t work_bytes = 0;
+        nvrx::rank_attribution_plan(a->R, a->K, a->top, nullptr, nullptr, &work_bytes);
+        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
+        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
+        NVRX_CHECK_ARG(a->loss_out, fn + ": null loss_out");
+        NVRX_CHECK_ARG(a->taken, fn + ": null taken");
+        NVRX_CHECK_ARG(a->positive, fn + ": null positive");
+        NVRX_CHECK_ARG(work_bytes == 0 || a->work, fn + ": null work (the plan needs work_bytes)");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->loss_out & 7) == 0, fn + ": loss_out not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->work & 7) == 0, fn + ": work not 8-byte aligned");
+    return hip_status(nvrx::rank_attribution(*a, S(stream)), fn.c_str());
+}
+
 // the conversion between the two histories (histogram_history_compact.hip): slots, not columns
 static int check_convert(const std::string& fn, const void* hist, const void* chist, int64_t R,
                          int64_t stride) {

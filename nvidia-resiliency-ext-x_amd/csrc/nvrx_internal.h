@@ -76,6 +76,11 @@ hipError_t histogram_history_scores_compact(const nvrx_histchist_args& a, hipStr
 // the individual tail score attribution of counts against the compact history
 // (histogram_history_compact_attribution.hip)
 hipError_t histogram_history_attribution_compact(const nvrx_histchistattr_args& a, hipStream_t st);
+// the ranks behind a kernel's tail loss: the column-wise top-k of a loss matrix and its host-side
+// launch plan (rank_attribution.hip)
+void rank_attribution_plan(int64_t R, int64_t K, int top, int64_t* tiles, int64_t* splits,
+                           int64_t* work_bytes);
+hipError_t rank_attribution(const nvrx_rankattr_args& a, hipStream_t st);
 hipError_t compact_history_from_dense(const uint32_t* hist, void* chist, int64_t R, int64_t stride,
                                       uint64_t* folded, hipStream_t st);
 hipError_t compact_history_to_dense(const void* chist, uint32_t* hist, int64_t R, int64_t stride,

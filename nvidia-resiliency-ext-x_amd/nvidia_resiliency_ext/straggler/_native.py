@@ -178,6 +178,13 @@ class HistCHistAttrArgs(ctypes.Structure):
     ]
 
 
+class RankAttrArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("loss", P), ("ld", i64), ("row_valid", P), ("top", i32),
+        ("idx", P), ("loss_out", P), ("taken", P), ("positive", P), ("work", P),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -238,6 +245,9 @@ SIGNATURES = {
     "nvrx_histogram_history_scores_compact": (ctypes.c_int, [ctypes.POINTER(HistCHistArgs), P]),
     "nvrx_histogram_history_attribution_compact": (ctypes.c_int,
                                                    [ctypes.POINTER(HistCHistAttrArgs), P]),
+    "nvrx_rank_attribution_plan": (ctypes.c_int, [i64, i64, i32, ctypes.POINTER(i64),
+                                                  ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+    "nvrx_rank_attribution": (ctypes.c_int, [ctypes.POINTER(RankAttrArgs), P]),
     "nvrx_compact_history_from_dense": (ctypes.c_int, [P, P, i64, i64, P, P]),
     "nvrx_compact_history_to_dense": (ctypes.c_int, [P, P, i64, i64, P]),
     "nvrx_kernel_ref": (ctypes.c_int, [P, P, i64, i64, P, P, P]),

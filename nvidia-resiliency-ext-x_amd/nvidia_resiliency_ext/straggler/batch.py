@@ -87,6 +87,16 @@ class BatchTailAttribution:
 
 
 @dataclass
+class BatchKernelRanks:
+    """``MatrixReporter.kernel_ranks``: per kernel the `top` ranks with the largest excess tail time,
+    largest first (ties: the lower rank)."""
+    rank: np.ndarray      # [K, top] i32 rank (-1: no further rank taken)
+    loss_ns: np.ndarray   # [K, top] f64 the matrix's element, bit for bit; NaN where rank is -1
+    taken: np.ndarray     # [K] i32 ranks taken: not NaN, and flagged when ``flagged`` is given
+    positive: np.ndarray  # [K] i32 taken ranks that lost time on the kernel at all (loss > 0)
+
+
+@dataclass
 class BatchTailScores:
     """MatrixReporter.tail_scores: per rank a score from the tails of the fleet's histograms."""
     score: np.ndarray             # [R] f64, about 1 healthy, lower = more time in the tail; NaN: no samples
@@ -358,6 +368,7 @@ class MatrixReporter:
         self._htail = None  # individual_tail_scores(): [R][K][240] history and packed outputs, likewise
         self._rtail = None  # tail_scores_records(): bucketing work tensors, fleet histogram, packed outputs
         self._ctail = None  # the compact methods (history="compact"): [R][K][64] history, packed outputs
+        self._kranks = {}  # kernel_ranks(): packed outputs, work space and row mask per top
         # half_life=: absorbing calls per history since its last aging or reset_tail_history
         self._absorbed = {"dense": 0, "compact": 0}
 
@@ -966,6 +977,59 @@ class MatrixReporter:
             out=ops.TailAttribution.packed(buf, R, top, t["loss_all"]))
         host = buf.cpu().numpy()  # the one device-to-host transfer (synchronizes)
         return BatchTailAttribution.unpack(host, R, top, t["loss_all"])
+
+    def kernel_ranks(self, loss_all: torch.Tensor, top: int = 8, flagged=None) -> BatchKernelRanks:
+        """The ranks behind a kernel's tail loss, the converse of ``attribute=``: per kernel the
+        `top` (1..16) ranks with the largest excess tail time in ``loss_all``, how many ranks are
+        taken and how many of them lose time on the kernel at all (loss > 0).  ``loss_all`` is the
+        float64 [R, K] device tensor of any ``...attribution.loss_all`` of this reporter
+        (``tail_scores``, ``individual_tail_scores``, the record-stream methods,
+        ``compact_tail_attribution``), or any other such tensor; NaN means not taken.  That tensor
+        is the reporter's WORKSPACE: the next ``attribute=`` call of the same family overwrites
+        it, so ask before that call.  ``flagged`` (bool / uint8 [R], a numpy array or a tensor,
+        e.g. a result's ``stragglers``) restricts the ranking to those ranks.  Ties go to the
+        lower rank, -0.0 and +0.0 tie, and ``loss_ns`` holds the matrix's own bits
+        (``ops.rank_attribution``: the matrix is read once on the device, never copied to the
+        host; ``histograms.rank_attribution`` is the host twin).  It queues behind reports in
+        flight and touches none of the report's buffers; its outputs and work space are allocated
+        once per reporter and `top`, and the results come in one device-to-host copy.  ValueError
+        for a wrong shape, dtype or device, before anything is allocated or launched.  It does
+        not look at ``exchange``: the matrix is whatever the caller holds.  Beyond the
+        reference."""
+        top, _ = ops.attribution_request(top, "relative")
+        R, K = self.R, self.K
+        if not isinstance(loss_all, torch.Tensor) or not loss_all.is_cuda or \
+                (self.device.index is not None and loss_all.device != self.device):
+            raise ValueError("loss_all must be a tensor on the reporter's device")
+        if loss_all.dtype != torch.float64 or tuple(loss_all.shape) != (R, K):
+            raise ValueError(f"loss_all must be a float64 tensor of shape [{R}, {K}]")
+        ops._rank_loss(loss_all)
+        rows = None
+        if flagged is not None:
+            rows = flagged if isinstance(flagged, torch.Tensor) else torch.from_numpy(np.asarray(flagged))
+            if rows.dtype not in (torch.bool, torch.uint8) or tuple(rows.shape) != (R,):
+                raise ValueError(f"flagged must be a bool / uint8 array or tensor of shape [{R}]")
+            if rows.is_cuda and rows.device != loss_all.device:
+                raise ValueError("flagged must be on the host or on loss_all's device")
+        d = loss_all.device
+        t = self._kranks.get(top)
+        if t is None:
+            need = ops.rank_attribution_plan(R, K, top)[2]
+            t = self._kranks[top] = dict(
+                buf=torch.zeros(ops.RankAttribution.nbytes(K, top), dtype=torch.uint8, device=d),
+                work=torch.empty(need, dtype=torch.uint8, device=d) if need else None,
+                rows=torch.empty(R, dtype=torch.uint8, device=d))
+        self._order_after_inflight()
+        if rows is not None:
+            if rows.is_cuda and rows.is_contiguous():
+                rows = rows.view(torch.uint8) if rows.dtype == torch.bool else rows
+            else:
+                t["rows"].copy_(rows.view(torch.uint8) if rows.dtype == torch.bool else rows)
+                rows = t["rows"]
+        ops.rank_attribution(loss_all, top, rows=rows, out=ops.RankAttribution.packed(t["buf"], K, top),
+                             work=t["work"])
+        host = t["buf"].cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        return BatchKernelRanks(*ops.RankAttribution.unpack(host, K, top))
 
     def convert_tail_history(self, to: str) -> Optional[np.ndarray]:
         """Move the reporter from one history of the individual tail scores to the other, on the

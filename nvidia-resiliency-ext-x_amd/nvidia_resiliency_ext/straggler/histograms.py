@@ -41,6 +41,8 @@ against it (``ops.segment_history_attribution_compact_ragged``,
 ``history_age`` / ``compact_age`` are the host twins of the aging of the two histories (every count
 shifted right, the compact entries that reach zero evicted; ``ops.histogram_history_age``,
 ``ops.compact_history_age``, ``MatrixReporter.age_tail_history``, ``half_life=``).
+``rank_attribution`` is the host twin of the converse of the attributions (``ops.rank_attribution``,
+``MatrixReporter.kernel_ranks``): per kernel the ranks with the largest loss in a ``loss_all``.
 """
 from __future__ import annotations
 
@@ -778,6 +780,49 @@ def segment_compact_history_attribution(keys, seg_off, seg_len, K: int, chist, p
     windows' counts."""
     return compact_history_attribution(segment_counts(keys, seg_off, seg_len, K, cap), chist,
                                        permille, top, hist_index, col_valid)
+
+
+@dataclass
+class RankAttribution:
+    """``rank_attribution``: per column (kernel) the ``top`` rows (ranks) with the largest loss,
+    largest first (ties: the lower row)."""
+    idx: np.ndarray       # [K, top] i32 row, -1 beyond the elements taken
+    loss: np.ndarray      # [K, top] f64 the input's value, bit for bit; NaN where idx is -1
+    taken: np.ndarray     # [K] i32 rows taken: valid and not NaN
+    positive: np.ndarray  # [K] i32 taken rows with loss > 0
+
+
+def rank_attribution(loss, top: int, rows=None) -> RankAttribution:
+    """The ranks behind a kernel's tail loss: per column of ``loss`` ([R, K] f64, e.g. the
+    ``loss_all`` of any attribution above) the ``top`` (1..16) rows with the largest loss.  An
+    element is taken iff it is not NaN and its row is on (``rows``: [R], zero = off; None: all
+    on).  Per column a stable sort of the rows by descending loss: the comparison is on values, so
+    -0.0 and +0.0 tie and the lower row goes first, while the loss returned is the input's element
+    (its sign kept).  The host twin of ``ops.rank_attribution`` / ``MatrixReporter.kernel_ranks``
+    with the same definition (include/nvrx_straggler.h)."""
+    if isinstance(top, bool) or int(top) != top or not 1 <= top <= 16:
+        raise ValueError(f"top must be an int in [1, 16], got {top!r}")
+    top = int(top)
+    x = np.asarray(loss, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("loss must have shape [R, K]")
+    R, K = x.shape
+    taken = ~np.isnan(x)
+    if rows is not None:
+        on = np.asarray(rows).astype(bool)
+        if on.shape != (R,):
+            raise ValueError("rows must have shape [R]")
+        taken &= on[:, None]
+    res = RankAttribution(np.full((K, top), -1, np.int32), np.full((K, top), np.nan),
+                          taken.sum(0).astype(np.int32), (taken & (x > 0.0)).sum(0).astype(np.int32))
+    # NaN keys (not taken) sort behind every value, +inf (a loss of -inf) included
+    order = np.argsort(np.where(taken, -x, np.nan), axis=0, kind="stable")[:top]
+    for j in range(order.shape[0]):
+        r, k = order[j], np.arange(K)
+        have = j < res.taken
+        res.idx[have, j] = r[have]
+        res.loss[have, j] = x[r[have], k[have]]
+    return res
 
 
 def quantile_bounds(counts, permille: int):

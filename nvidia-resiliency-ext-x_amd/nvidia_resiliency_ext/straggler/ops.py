@@ -1089,6 +1089,112 @@ def histogram_history_attribution_compact(counts: torch.Tensor, chist: torch.Ten
     return out
 
 
+@dataclass
+class RankAttribution:
+    """Per column (kernel) of ``rank_attribution`` (device tensors), the ``top`` rows (ranks) with
+    the largest loss, largest first: idx [K, top] int32 row (-1: fewer rows taken), loss [K, top]
+    float64 with the input's bits (NaN where idx is -1), taken [K] int32 rows taken, positive [K]
+    int32 taken rows whose loss is > 0."""
+
+    idx: torch.Tensor
+    loss: torch.Tensor
+    taken: torch.Tensor
+    positive: torch.Tensor
+
+    @staticmethod
+    def nbytes(K: int, top: int) -> int:
+        """Bytes of the packed form: loss (8), idx (4) per (column, j); taken, positive (4 each)."""
+        return 12 * K * top + 8 * K
+
+    @classmethod
+    def empty(cls, K: int, top: int, device) -> "RankAttribution":
+        return cls.packed(torch.empty(cls.nbytes(K, top), dtype=torch.uint8, device=device), K, top)
+
+    @classmethod
+    def packed(cls, buf: torch.Tensor, K: int, top: int) -> "RankAttribution":
+        """Views of the outputs in one 8-byte aligned uint8 buffer of ``nbytes(K, top)`` bytes (the
+        f64 field first), so that one copy moves them all; ``unpack`` reads it back."""
+        n = K * top
+        d = buf[8 * n:12 * n + 8 * K].view(torch.int32)
+        return cls(d[:n].view(K, top), buf[:8 * n].view(torch.float64).view(K, top),
+                   d[n:n + K], d[n + K:n + 2 * K])
+
+    @staticmethod
+    def unpack(host: np.ndarray, K: int, top: int):
+        """The host copy of a ``packed`` buffer as numpy arrays: (idx [K, top] i32, loss [K, top]
+        f64, taken [K] i32, positive [K] i32)."""
+        n = K * top
+        d = host[8 * n:12 * n + 8 * K].view(np.int32).copy()
+        return (d[:n].reshape(K, top), host[:8 * n].view(np.float64).reshape(K, top).copy(),
+                d[n:n + K], d[n + K:n + 2 * K])
+
+
+def rank_attribution_plan(R: int, K: int, top: int):
+    """(tiles, splits, work_bytes) of ``rank_attribution`` on an [R, K] matrix: workgroups along K
+    (64 columns each) and along R, and the bytes of ``work`` it needs (0 with one split, where one
+    kernel writes the outputs; more splits add a merge kernel).  Pure host code."""
+    t, s, w = N.i64(), N.i64(), N.i64()
+    N.call("nvrx_rank_attribution_plan", R, K, top, ctypes.byref(t), ctypes.byref(s), ctypes.byref(w))
+    return t.value, s.value, w.value
+
+
+def _rank_loss(loss):
+    """loss of ``rank_attribution``: a float64 device tensor [R, K] whose rows are contiguous and a
+    whole number of elements apart (a row stride above K is allowed); returns (R, K, ld)."""
+    N.require_device(loss, "loss")
+    if loss.dtype != torch.float64 or loss.dim() != 2:
+        raise ValueError("loss must be a float64 device tensor of shape [R, K]")
+    R, K = loss.shape
+    ld = K
+    if R > 0 and K > 0:
+        if K > 1 and loss.stride(1) != 1:
+            raise ValueError("loss must have contiguous rows (stride 1 along K)")
+        if R > 1:
+            ld = loss.stride(0)
+            if ld < K:
+                raise ValueError("loss must have a row stride of at least K elements")
+        if R * ld >= 1 << 31:
+            raise ValueError("R * row stride must be below 2^31")
+    return R, K, ld
+
+
+def rank_attribution(loss: torch.Tensor, top: int = 8, rows: Optional[torch.Tensor] = None,
+                     out: Optional[RankAttribution] = None, work: Optional[torch.Tensor] = None,
+                     stream=None) -> RankAttribution:
+    """The ranks behind a kernel's tail loss (no reference counterpart): per column of ``loss``
+    (float64 [R, K] on the device, e.g. the ``loss_all`` of any tail attribution; rows contiguous,
+    a row stride above K allowed) the ``top`` (1..16) rows with the largest loss.  A NaN is not
+    taken, nor is any element of a row with ``rows[r] == 0`` (``rows``: uint8 / bool [R], e.g. a
+    score call's ``strag``).  Ties go to the lower row, -0.0 and +0.0 tie, and ``out.loss`` holds
+    the input's bits (``histograms.rank_attribution`` is the host twin).  ``work`` (uint8, 8-byte
+    aligned, at least ``rank_attribution_plan(R, K, top)[2]`` bytes) is allocated when the plan
+    needs one and none is given.  One or two launches, the matrix read once; no scratch."""
+    top, _ = attribution_request(top, "relative")
+    R, K, ld = _rank_loss(loss)
+    d = loss.device
+    _u8_vector(rows, "rows", R)
+    if out is None:
+        out = RankAttribution.empty(K, top, d)
+    _tail_tensor(out.idx, "out.idx", torch.int32, (K, top))
+    _tail_tensor(out.loss, "out.loss", torch.float64, (K, top))
+    _tail_tensor(out.taken, "out.taken", torch.int32, (K,))
+    _tail_tensor(out.positive, "out.positive", torch.int32, (K,))
+    need = rank_attribution_plan(R, K, top)[2]
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=d) if need else None
+    else:
+        N.require_device(work, "work")
+        if (work.dtype != torch.uint8 or not work.is_contiguous() or work.numel() < need or
+                work.data_ptr() % 8):
+            raise ValueError(f"work must be a contiguous, 8-byte aligned uint8 tensor of at least "
+                             f"{need} bytes (rank_attribution_plan)")
+    a = N.RankAttrArgs(R, K, loss.data_ptr(), ld, N.ptr(rows), top, out.idx.data_ptr(),
+                       out.loss.data_ptr(), out.taken.data_ptr(), out.positive.data_ptr(),
+                       N.ptr(work))
+    N.call("nvrx_rank_attribution", ctypes.byref(a), _stream(stream))
+    return out
+
+
 def kernel_ref(num: torch.Tensor, med: torch.Tensor, ref: Optional[torch.Tensor] = None,
                scratch: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """ref[k] = min_r med[r, k] if every row has k (num > 0), else NaN (reporting.py:255-296)."""
