@@ -37,7 +37,8 @@
  * nvrx_segment_history_scores_compact_ragged, nvrx_segment_history_attribution_compact_ragged,
  * nvrx_compact_history_age, nvrx_histogram_history_age, nvrx_histogram_history_scores_compact,
  * nvrx_compact_history_from_dense, nvrx_compact_history_to_dense,
- * nvrx_histogram_history_attribution_compact, nvrx_rank_attribution / _plan.
+ * nvrx_histogram_history_attribution_compact, nvrx_rank_attribution / _plan,
+ * nvrx_score_rank_attribution.
  */
 #ifndef NVRX_STRAGGLER_H
 #define NVRX_STRAGGLER_H
@@ -917,7 +918,8 @@ int nvrx_histogram_history_attribution_compact(const nvrx_histchistattr_args* ar
  *   outputs, more a second kernel that merges the splits' partial lists) and work_bytes (0 with one
  *   split).  work_bytes does not decrease as R or top grow with the other two fixed.  R == 0 or
  *   K == 0: tiles 0, splits 1, work_bytes 0.  Any output pointer may be NULL.  Negative R or K or a
- *   top out of range is an error.
+ *   top out of range is an error.  One plan serves both entries: nvrx_score_rank_attribution
+ *   (below) launches the same grid and sizes and lays out `work` the same way.
  * nvrx_rank_attribution: `work` is device memory of at least work_bytes, 8-byte aligned (may be
  *   NULL when work_bytes is 0); its content is unspecified afterwards.  R * ld below 2^31.  R == 0
  *   or K == 0 launches nothing and leaves the outputs untouched.  A top out of range, ld below K, a
@@ -1021,6 +1023,60 @@ typedef struct nvrx_attribution_args {
     int32_t* err;   /* [1] or NULL */
 } nvrx_attribution_args;
 int nvrx_score_attribution(const nvrx_attribution_args* args, void* stream);
+
+/* Score rank attribution: the ranks behind a kernel's score loss.  No reference counterpart.  The
+ * converse of "Score attribution" above, as "Rank attribution" is the converse of the tail
+ * attributions: per kernel, the `top` ranks that lose the most on it, and how many lose anything.
+ * The definition is part of the ABI.
+ * Inputs: the input fields of nvrx_attribution_args with the same meaning (R, K, value_f64, num,
+ * med, avg, col_valid, ref, ref_index, ref_missing, hist, hist_index, hist_stride, kind); the
+ * history is READ ONLY.  row_valid u8 [R] or NULL and top as in nvrx_rankattr_args.
+ * Let L[r][k] be the element's loss exactly as nvrx_score_attribution defines it (f64, every
+ * operation rounded separately:  m = MED;  w = NUM * AVG;  s = base / m;  loss = w * (1.0 - s))
+ * where nvrx_score_attribution would take the element -- it is eligible for `kind`, MED != 0 and
+ * the loss is not NaN -- and NaN where it would not.  An eligible element with MED == 0 in a row
+ * that is valid sets *err |= 1 (err may be NULL; it is not written otherwise).  Outputs:
+ *     idx [K][top], loss [K][top], taken [K], positive [K]   equal, bit for bit, to what
+ *                     nvrx_rank_attribution writes for the matrix L with the same row_valid and top
+ *                     (ties to the lower row, -0.0 ties with +0.0, -1 / NaN beyond the taken)
+ *     score [K][top]  f64: the winner's s; NaN where idx = -1
+ * The stored loss and score are recomputed from the inputs at the winner's (row, column), never
+ * rebuilt from a sort key: a -0.0 loss stays -0.0.  No f64 column sums: they would depend on the
+ * order of the additions.  L itself is never stored.
+ * ONE PLAN SERVES BOTH ENTRIES: the grid and `work` are those of nvrx_rank_attribution_plan(R, K,
+ * top) -- same tiles, same splits, same work_bytes, same layout of the partial lists.  `work` is
+ * device memory of at least work_bytes, 8-byte aligned (may be NULL when work_bytes is 0); its
+ * content is unspecified afterwards.  R and K below 2^31.  R == 0 or K == 0 launches nothing and
+ * leaves the outputs untouched.  A top or kind out of range, a missing input or output, a kind
+ * without its base, hist_index without hist_stride, a missing work where the plan needs one, or a
+ * misaligned loss, score or work is an error.  Stream-ordered: one or two kernels on `stream` only:
+ * no allocation, no synchronisation, no host read-back, no clear, no scratch, no atomics other than
+ * the OR into err; capturable as a linear chain with the calls around it.  Two calls on the same
+ * inputs write the same bytes whatever `work` held. */
+typedef struct nvrx_scorerank_args {
+    int64_t R, K;
+    int32_t value_f64;
+    const int32_t* num;
+    const void* med;
+    const void* avg;
+    const uint8_t* col_valid;
+    const float* ref;
+    const int32_t* ref_index;
+    const uint32_t* ref_missing;
+    const void* hist;
+    const int32_t* hist_index;
+    int64_t hist_stride;
+    int32_t kind, top;
+    const uint8_t* row_valid;   /* [R] or NULL */
+    int32_t* idx;               /* [K][top] */
+    double* loss;               /* [K][top] */
+    double* score;              /* [K][top] */
+    int32_t* taken;             /* [K] */
+    int32_t* positive;          /* [K] */
+    int32_t* err;               /* [1] or NULL */
+    void* work;                 /* work_bytes of nvrx_rank_attribution_plan, or NULL when 0 */
+} nvrx_scorerank_args;
+int nvrx_score_rank_attribution(const nvrx_scorerank_args* args, void* stream);
 
 /* Statistics of section CPU timings (ms, float64): section s = vals[off[s] : off[s+1]]
  * (off: [nsec+1], device).  MIN, MAX, MED = lower median s[(n-1)/2] (torch.median),

@@ -813,6 +813,40 @@ int nvrx_score_attribution(const nvrx_attribution_args* a, void* stream) {
     return hip_status(nvrx::score_attribution(*a, S(stream)), "nvrx_score_attribution");
 }
 
+// the ranks behind a kernel's score loss (score_rank_attribution.hip): nvrx_score_attribution's
+// input checks, nvrx_rank_attribution's request, outputs and work
+int nvrx_score_rank_attribution(const nvrx_scorerank_args* a, void* stream) {
+    const std::string fn("nvrx_score_rank_attribution");
+    NVRX_CHECK_ARG(a, fn + ": null args");
+    if (int rc = check_rank_request(fn, a->R, a->K, a->top)) return rc;
+    NVRX_CHECK_ARG(a->kind == NVRX_ATTR_RELATIVE || a->kind == NVRX_ATTR_INDIVIDUAL,
+                   fn + ": unknown kind (NVRX_ATTR_RELATIVE or NVRX_ATTR_INDIVIDUAL)");
+    NVRX_CHECK_ARG(a->R < (int64_t)1 << 31, fn + ": R must be below 2^31");
+    NVRX_CHECK_ARG(a->K < (int64_t)1 << 31, fn + ": K must be below 2^31");
+    NVRX_CHECK_ARG(a->value_f64 == 0 || a->value_f64 == 1, fn + ": bad value_f64");
+    NVRX_CHECK_ARG(!a->hist_index || a->hist_stride > 0, fn + ": hist_index requires hist_stride");
+    if (a->R > 0 && a->K > 0) {
+        int64_t work_bytes = 0;
+        nvrx::rank_attribution_plan(a->R, a->K, a->top, nullptr, nullptr, &work_bytes);
+        NVRX_CHECK_ARG(a->num, fn + ": null num");
+        NVRX_CHECK_ARG(a->med, fn + ": null med");
+        NVRX_CHECK_ARG(a->avg, fn + ": null avg");
+        NVRX_CHECK_ARG(a->idx, fn + ": null idx");
+        NVRX_CHECK_ARG(a->loss, fn + ": null loss");
+        NVRX_CHECK_ARG(a->score, fn + ": null score");
+        NVRX_CHECK_ARG(a->taken, fn + ": null taken");
+        NVRX_CHECK_ARG(a->positive, fn + ": null positive");
+        NVRX_CHECK_ARG(a->kind != NVRX_ATTR_RELATIVE || a->ref, fn + ": the relative kind needs ref");
+        NVRX_CHECK_ARG(a->kind != NVRX_ATTR_INDIVIDUAL || a->hist,
+                       fn + ": the individual kind needs hist");
+        NVRX_CHECK_ARG(work_bytes == 0 || a->work, fn + ": null work (the plan needs work_bytes)");
+    }
+    NVRX_CHECK_ARG(((uintptr_t)a->loss & 7) == 0, fn + ": loss not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->score & 7) == 0, fn + ": score not 8-byte aligned");
+    NVRX_CHECK_ARG(((uintptr_t)a->work & 7) == 0, fn + ": work not 8-byte aligned");
+    return hip_status(nvrx::score_rank_attribution(*a, S(stream)), fn.c_str());
+}
+
 int nvrx_finalize_scores(const double* partials, int64_t R, int64_t nshards, int32_t round_f32,
                          double thr_rel, double thr_ind, double* gpu_rel, double* gpu_ind,
                          uint8_t* strag_rel, uint8_t* strag_ind, int32_t* err, void* stream) {

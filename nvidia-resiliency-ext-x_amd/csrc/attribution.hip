@@ -19,26 +19,10 @@
 
 #include "nvrx_common.h"
 #include "nvrx_internal.h"
+#include "score_element.h"
 #include "topk_select.h"
 
 namespace nvrx {
-
-namespace {
-
-// One element's terms; false when the element is not taken (absent, filtered, no base, MED == 0,
-// NaN loss).  zero_med reports an eligible element with MED == 0.
-template <typename T>
-__device__ __forceinline__ bool element_terms(bool eligible, int32_t nm, T mt, T av, double base,
-                                              double& w, double& s, double& loss, bool& zero_med) {
-    const double m = (double)mt;
-    w = (double)nm * (double)av;
-    s = base / m;
-    loss = w * (1.0 - s);
-    zero_med = eligible && m == 0.0;
-    return eligible && m != 0.0 && loss == loss;
-}
-
-}  // namespace
 
 template <typename T, int TOP>
 __global__ __launch_bounds__(256) void attribution_kernel(nvrx_attribution_args a) {

@@ -99,6 +99,9 @@ hipError_t pack_min_times(const double* med, const int32_t* ids, int64_t n, floa
 hipError_t scores(const nvrx_score_args& a, hipStream_t st);
 // attribution.hip: per row, the `top` largest losses w*(1 - s) behind the score
 hipError_t score_attribution(const nvrx_attribution_args& a, hipStream_t st);
+// score_rank_attribution.hip: per column, the `top` rows with the largest of those losses, on
+// rank_attribution_plan's grid and work
+hipError_t score_rank_attribution(const nvrx_scorerank_args& a, hipStream_t st);
 hipError_t finalize_scores(const double* partials, int64_t R, int64_t nshards, int round_f32,
                            double thr_rel, double thr_ind, double* gpu_rel, double* gpu_ind,
                            uint8_t* strag_rel, uint8_t* strag_ind, int32_t* err, hipStream_t st);

@@ -185,6 +185,18 @@ class RankAttrArgs(ctypes.Structure):
     ]
 
 
+class ScoreRankArgs(ctypes.Structure):
+    _fields_ = [
+        ("R", i64), ("K", i64), ("value_f64", i32),
+        ("num", P), ("med", P), ("avg", P), ("col_valid", P),
+        ("ref", P), ("ref_index", P), ("ref_missing", P),
+        ("hist", P), ("hist_index", P), ("hist_stride", i64),
+        ("kind", i32), ("top", i32), ("row_valid", P),
+        ("idx", P), ("loss", P), ("score", P), ("taken", P), ("positive", P), ("err", P),
+        ("work", P),
+    ]
+
+
 class Record(ctypes.Structure):
     _fields_ = [("slot", u32), ("ns", u32)]
 
@@ -254,6 +266,7 @@ SIGNATURES = {
     "nvrx_pack_min_times": (ctypes.c_int, [P, P, i64, P, i64, P]),
     "nvrx_scores": (ctypes.c_int, [ctypes.POINTER(ScoreArgs), P]),
     "nvrx_score_attribution": (ctypes.c_int, [ctypes.POINTER(AttributionArgs), P]),
+    "nvrx_score_rank_attribution": (ctypes.c_int, [ctypes.POINTER(ScoreRankArgs), P]),
     "nvrx_finalize_scores": (ctypes.c_int, [P, i64, i64, i32, f64, f64, P, P, P, P, P, P]),
     "nvrx_section_scores": (ctypes.c_int, [P, P, i64, i64, P, P, P, P, i32, P, P, P, P]),
     "nvrx_stragglers": (ctypes.c_int, [P, i64, f64, P, P]),

@@ -97,6 +97,42 @@ class BatchKernelRanks:
 
 
 @dataclass
+class BatchScoreKernelRanks:
+    """``MatrixReporter.score_kernel_ranks``: per kernel the `top` ranks with the largest loss
+    ``NUM*AVG * (1 - base/MED)`` behind the median scores, largest first (ties: the lower rank)."""
+    rank: np.ndarray      # [K, top] i32 rank (-1: no further rank taken)
+    loss_us: np.ndarray   # [K, top] f64 the rank's loss on the kernel, NaN where rank is -1
+    score: np.ndarray     # [K, top] f64 base/MED of that rank on the kernel
+    taken: np.ndarray     # [K] i32 ranks taken: scored on the kernel, and flagged when ``flagged`` is given
+    positive: np.ndarray  # [K] i32 taken ranks that lose on the kernel at all (loss > 0)
+    err: int = 0          # 1: some scored MED was 0 (that element is left out)
+
+
+def _flagged_rows(flagged, R: int, device):
+    """``flagged`` of the kernel-ranks calls as a tensor (None: every rank): bool / uint8 [R], a
+    numpy array or a tensor on the host or on ``device``; ValueError if not."""
+    if flagged is None:
+        return None
+    rows = flagged if isinstance(flagged, torch.Tensor) else torch.from_numpy(np.asarray(flagged))
+    if rows.dtype not in (torch.bool, torch.uint8) or tuple(rows.shape) != (R,):
+        raise ValueError(f"flagged must be a bool / uint8 array or tensor of shape [{R}]")
+    if rows.is_cuda and rows.device != device:
+        raise ValueError("flagged must be on the host or on the reporter's device")
+    return rows
+
+
+def _rows_on_device(rows, scratch: torch.Tensor):
+    """The checked ``flagged`` as the uint8 device vector the kernels read: itself when it is
+    already one, else copied into ``scratch`` (uint8 [R] on the device)."""
+    if rows is None:
+        return None
+    if rows.is_cuda and rows.is_contiguous():
+        return rows.view(torch.uint8) if rows.dtype == torch.bool else rows
+    scratch.copy_(rows.view(torch.uint8) if rows.dtype == torch.bool else rows)
+    return scratch
+
+
+@dataclass
 class BatchTailScores:
     """MatrixReporter.tail_scores: per rank a score from the tails of the fleet's histograms."""
     score: np.ndarray             # [R] f64, about 1 healthy, lower = more time in the tail; NaN: no samples
@@ -369,6 +405,7 @@ class MatrixReporter:
         self._rtail = None  # tail_scores_records(): bucketing work tensors, fleet histogram, packed outputs
         self._ctail = None  # the compact methods (history="compact"): [R][K][64] history, packed outputs
         self._kranks = {}  # kernel_ranks(): packed outputs, work space and row mask per top
+        self._sranks = {}  # score_kernel_ranks(): likewise, plus the error word
         # half_life=: absorbing calls per history since its last aging or reset_tail_history
         self._absorbed = {"dense": 0, "compact": 0}
 
@@ -1004,13 +1041,7 @@ class MatrixReporter:
         if loss_all.dtype != torch.float64 or tuple(loss_all.shape) != (R, K):
             raise ValueError(f"loss_all must be a float64 tensor of shape [{R}, {K}]")
         ops._rank_loss(loss_all)
-        rows = None
-        if flagged is not None:
-            rows = flagged if isinstance(flagged, torch.Tensor) else torch.from_numpy(np.asarray(flagged))
-            if rows.dtype not in (torch.bool, torch.uint8) or tuple(rows.shape) != (R,):
-                raise ValueError(f"flagged must be a bool / uint8 array or tensor of shape [{R}]")
-            if rows.is_cuda and rows.device != loss_all.device:
-                raise ValueError("flagged must be on the host or on loss_all's device")
+        rows = _flagged_rows(flagged, R, loss_all.device)
         d = loss_all.device
         t = self._kranks.get(top)
         if t is None:
@@ -1020,12 +1051,7 @@ class MatrixReporter:
                 work=torch.empty(need, dtype=torch.uint8, device=d) if need else None,
                 rows=torch.empty(R, dtype=torch.uint8, device=d))
         self._order_after_inflight()
-        if rows is not None:
-            if rows.is_cuda and rows.is_contiguous():
-                rows = rows.view(torch.uint8) if rows.dtype == torch.bool else rows
-            else:
-                t["rows"].copy_(rows.view(torch.uint8) if rows.dtype == torch.bool else rows)
-                rows = t["rows"]
+        rows = _rows_on_device(rows, t["rows"])
         ops.rank_attribution(loss_all, top, rows=rows, out=ops.RankAttribution.packed(t["buf"], K, top),
                              work=t["work"])
         host = t["buf"].cpu().numpy()  # the one device-to-host transfer (synchronizes)
@@ -1173,6 +1199,59 @@ class MatrixReporter:
             share = loss / wsum[:, None]
         return BatchAttribution(h32[:n].reshape(R, top).copy(), loss,
                                 h64[n:2 * n].reshape(R, top).copy(), share, wsum, int(h32[n]))
+
+    def score_kernel_ranks(self, top: int = 8, kind: str = "relative",
+                           flagged=None) -> BatchScoreKernelRanks:
+        """The ranks behind a kernel's score loss, the converse of ``attribute``: per kernel the
+        `top` (1..16) ranks with the largest loss ``NUM*AVG * (1 - base/MED)``, how many ranks are
+        scored on the kernel and how many of them lose on it at all (loss > 0) -- one bad
+        collective on one node, or many unrelated kernels?  It explains the statistics in the
+        reporter's own buffer set, exactly as ``attribute`` does (relative: the reference is
+        recomputed into ``attribute``'s buffers; individual: the history is read, never written),
+        and changes none of the report's buffers.  ``flagged`` (bool / uint8 [R], a numpy array or
+        a tensor, e.g. a result's ``stragglers_relative``) restricts the ranking to those ranks.
+        Ties go to the lower rank, -0.0 and +0.0 tie (``ops.score_rank_attribution``: the [R, K]
+        loss matrix is never built; ``histograms.score_rank_attribution`` is the host twin).  It
+        queues behind reports in flight; its outputs and work space are allocated once per
+        reporter and `top`, and the results come in one device-to-host copy.  ValueError /
+        RuntimeError before anything is allocated or launched.  Beyond the reference."""
+        top, _ = ops.attribution_request(top, kind)
+        if self.exchange:
+            raise NotImplementedError("MatrixReporter.score_kernel_ranks: attribution across "
+                                      "kernel shards (exchange=True) is not supported")
+        if not (self.relative if kind == "relative" else self.individual):
+            raise RuntimeError(f"MatrixReporter.score_kernel_ranks: the reporter was built without "
+                               f"{kind} scores")
+        R, K, d = self.R, self.K, self.device
+        rows = _flagged_rows(flagged, R, self.own.stats.num.device)
+        t = self._sranks.get(top)
+        if t is None:  # packed outputs, then the error word
+            need = ops.rank_attribution_plan(R, K, top)[2]
+            nb = ops.ScoreRankAttribution.nbytes(K, top)
+            t = self._sranks[top] = dict(
+                buf=torch.zeros(nb + 8, dtype=torch.uint8, device=d),
+                work=torch.empty(need, dtype=torch.uint8, device=d) if need else None,
+                rows=torch.empty(R, dtype=torch.uint8, device=d))
+        self._order_after_inflight()
+        st = self.own.stats.view(R, K)
+        nb = ops.ScoreRankAttribution.nbytes(K, top)
+        err = t["buf"][nb:nb + 4].view(torch.int32)
+        err.zero_()
+        rows = _rows_on_device(rows, t["rows"])
+        ref = None
+        if kind == "relative":
+            if self._attr_ref is None:
+                self._attr_ref = (torch.empty(max(K, 1), dtype=torch.float32, device=d),
+                                  torch.empty(2 * max(K, 1), dtype=torch.int32, device=d))
+            ref = ops.kernel_ref(st.num, st.med, ref=self._attr_ref[0], scratch=self._attr_ref[1])
+        ops.score_rank_attribution(st.num, st.med, st.avg, top=top, kind=kind,
+                                   col_valid=self.col_valid, ref=ref,
+                                   hist=self.hist if kind == "individual" else None, rows=rows,
+                                   err=err, out=ops.ScoreRankAttribution.packed(t["buf"][:nb], K, top),
+                                   work=t["work"])
+        host = t["buf"].cpu().numpy()  # the one device-to-host transfer (synchronizes)
+        return BatchScoreKernelRanks(*ops.ScoreRankAttribution.unpack(host[:nb], K, top),
+                                     int(host[nb:nb + 4].view(np.int32)[0]))
 
     def graph(self, ns: torch.Tensor, s_push: int) -> "ReportGraph":
         """The report's device work captured once as HIP graphs, replayed per report (the

@@ -43,6 +43,10 @@ shifted right, the compact entries that reach zero evicted; ``ops.histogram_hist
 ``ops.compact_history_age``, ``MatrixReporter.age_tail_history``, ``half_life=``).
 ``rank_attribution`` is the host twin of the converse of the attributions (``ops.rank_attribution``,
 ``MatrixReporter.kernel_ranks``): per kernel the ranks with the largest loss in a ``loss_all``.
+``score_losses`` / ``score_rank_attribution`` are the host twins of the same question about the
+median scores (``ops.score_rank_attribution``, ``MatrixReporter.score_kernel_ranks``): the loss
+``NUM*AVG * (1 - base/MED)`` of every element a score takes, and per kernel the ranks with the
+largest.
 """
 from __future__ import annotations
 
@@ -823,6 +827,81 @@ def rank_attribution(loss, top: int, rows=None) -> RankAttribution:
         res.idx[have, j] = r[have]
         res.loss[have, j] = x[r[have], k[have]]
     return res
+
+
+def score_losses(num, med, avg, kind: str, col_valid=None, ref=None, ref_index=None,
+                 ref_missing=None, hist=None, hist_index=None, hist_stride: int = 0, rows=None):
+    """Every element's loss behind the median scores, as ``ops.score_attribution`` defines it:
+    ``(loss_all, s_all, err)`` with ``loss_all`` [R, K] f64 the loss where the element is taken and
+    NaN where it is not, ``s_all`` [R, K] f64 its ``s`` (whatever the arithmetic gives where not
+    taken), ``err`` 1 when an eligible MED is 0 (in a row that is on, when ``rows`` is given).
+    Per element in f64, one operation per statement: ``m = MED; w = NUM * AVG; s = base / m;
+    loss = w * (1 - s)``.  Eligible: ``col_valid`` None or nonzero, ``num > 0``, and for
+    ``kind="relative"`` a reference ``ref[ref_index[k]] >= 0`` (-1 and NaN: none) not flagged in
+    ``ref_missing``; ``kind="individual"`` takes ``hist[r, hist_index[k]]`` (rows ``hist_stride``
+    apart) as it stands.  Taken: eligible, MED != 0 and the loss not NaN."""
+    if kind not in ("relative", "individual"):
+        raise ValueError(f"kind must be 'relative' or 'individual', got {kind!r}")
+    num, med, avg = np.asarray(num), np.asarray(med), np.asarray(avg)
+    if med.ndim != 2 or num.shape != med.shape or avg.shape != med.shape:
+        raise ValueError("num, med and avg must share one shape [R, K]")
+    R, K = med.shape
+    cols = np.arange(K)
+    elig = num > 0
+    if col_valid is not None:
+        elig = elig & (np.asarray(col_valid) != 0)[None, :]
+    if kind == "relative":
+        if ref is None:
+            raise ValueError("kind='relative' needs ref")
+        ri = cols if ref_index is None else np.asarray(ref_index)
+        b32 = np.asarray(ref, np.float32)[ri]
+        with np.errstate(invalid="ignore"):
+            usable = b32 >= 0  # -1 and NaN: no reference
+        if ref_missing is not None:
+            usable = usable & (np.asarray(ref_missing)[ri] == 0)
+        elig = elig & usable[None, :]
+        base = np.broadcast_to(b32.astype(np.float64)[None, :], (R, K))
+    else:
+        if hist is None:
+            raise ValueError("kind='individual' needs hist")
+        hi = cols if hist_index is None else np.asarray(hist_index)
+        flat = np.asarray(hist).reshape(-1)
+        base = flat[(np.arange(R) * (hist_stride or K))[:, None] + hi[None, :]].astype(np.float64)
+    with np.errstate(all="ignore"):
+        m = med.astype(np.float64)
+        w = num.astype(np.float64) * avg.astype(np.float64)
+        s = base / m
+        d = 1.0 - s
+        loss = w * d
+    zero = elig & (m == 0.0)
+    if rows is not None:
+        zero = zero & np.asarray(rows).astype(bool)[:, None]
+    take = elig & (m != 0.0) & ~np.isnan(loss)
+    return np.where(take, loss, np.nan), s, int(zero.any())
+
+
+@dataclass
+class ScoreRankAttribution:
+    """``score_rank_attribution``: ``RankAttribution`` of the score losses plus the winners' s."""
+    idx: np.ndarray       # [K, top] i32 row, -1 beyond the elements taken
+    loss: np.ndarray      # [K, top] f64 the element's loss; NaN where idx is -1
+    score: np.ndarray     # [K, top] f64 the element's s = base / MED; NaN where idx is -1
+    taken: np.ndarray     # [K] i32 rows taken
+    positive: np.ndarray  # [K] i32 taken rows with loss > 0
+    err: int = 0          # 1: an eligible MED of a row that is on was 0
+
+
+def score_rank_attribution(num, med, avg, top: int, kind: str, rows=None,
+                           **base) -> ScoreRankAttribution:
+    """The ranks behind a kernel's score loss: ``rank_attribution(loss_all, top, rows)`` over the
+    ``loss_all`` of ``score_losses(num, med, avg, kind, **base)``, plus the winners' ``s``.  The
+    host twin of ``ops.score_rank_attribution`` / ``MatrixReporter.score_kernel_ranks``."""
+    loss_all, s_all, err = score_losses(num, med, avg, kind, rows=rows, **base)
+    r = rank_attribution(loss_all, top, rows)
+    score = np.full(r.idx.shape, np.nan)
+    k, j = np.nonzero(r.idx >= 0)
+    score[k, j] = s_all[r.idx[k, j], k]
+    return ScoreRankAttribution(r.idx, r.loss, score, r.taken, r.positive, err)
 
 
 def quantile_bounds(counts, permille: int):

@@ -1309,6 +1309,113 @@ def score_attribution(num, med, avg, *, top, kind, col_valid=None, ref=None, ref
     return out
 
 
+@dataclass
+class ScoreRankAttribution:
+    """Per column (kernel) of ``score_rank_attribution`` (device tensors), the ``top`` rows (ranks)
+    with the largest loss w*(1 - s), largest first: idx [K, top] int32 row (-1: fewer rows taken),
+    loss / score [K, top] float64 (NaN where idx is -1), taken [K] int32 rows taken, positive [K]
+    int32 taken rows whose loss is > 0."""
+
+    idx: torch.Tensor
+    loss: torch.Tensor
+    score: torch.Tensor
+    taken: torch.Tensor
+    positive: torch.Tensor
+
+    @staticmethod
+    def nbytes(K: int, top: int) -> int:
+        """Bytes of the packed form: loss, score (8 each), idx (4) per (column, j); taken, positive
+        (4 each)."""
+        return 20 * K * top + 8 * K
+
+    @classmethod
+    def empty(cls, K: int, top: int, device) -> "ScoreRankAttribution":
+        return cls.packed(torch.empty(cls.nbytes(K, top), dtype=torch.uint8, device=device), K, top)
+
+    @classmethod
+    def packed(cls, buf: torch.Tensor, K: int, top: int) -> "ScoreRankAttribution":
+        """Views of the outputs in one 8-byte aligned uint8 buffer of ``nbytes(K, top)`` bytes (the
+        f64 fields first), so that one copy moves them all; ``unpack`` reads it back."""
+        n = K * top
+        f = buf[:16 * n].view(torch.float64)
+        d = buf[16 * n:20 * n + 8 * K].view(torch.int32)
+        return cls(d[:n].view(K, top), f[:n].view(K, top), f[n:].view(K, top),
+                   d[n:n + K], d[n + K:n + 2 * K])
+
+    @staticmethod
+    def unpack(host: np.ndarray, K: int, top: int):
+        """The host copy of a ``packed`` buffer as numpy arrays: (idx [K, top] i32, loss [K, top]
+        f64, score [K, top] f64, taken [K] i32, positive [K] i32)."""
+        n = K * top
+        f = host[:16 * n].view(np.float64).copy()
+        d = host[16 * n:20 * n + 8 * K].view(np.int32).copy()
+        return (d[:n].reshape(K, top), f[:n].reshape(K, top), f[n:].reshape(K, top),
+                d[n:n + K], d[n + K:n + 2 * K])
+
+
+def score_rank_attribution(num, med, avg, *, top, kind, col_valid=None, ref=None, ref_index=None,
+                           ref_missing=None, hist=None, hist_index=None, hist_stride=0, rows=None,
+                           err=None, out: Optional[ScoreRankAttribution] = None,
+                           work: Optional[torch.Tensor] = None, stream=None) -> ScoreRankAttribution:
+    """The ranks behind a kernel's score loss (no reference counterpart): the converse of
+    ``score_attribution``.  Inputs as ``score_attribution``; per column the ``top`` (1..16) rows
+    with the largest ``loss = NUM*AVG * (1 - base/MED)`` among the elements ``score_attribution``
+    would take, exactly what ``rank_attribution`` gives for the matrix of those losses (NaN where
+    not taken) -- which is never built -- plus the winners' ``s``.  ``rows`` (uint8 / bool [R]):
+    a row with 0 is not taken.  err (int32 [1], optional) is OR-ed with 1 when an eligible MED of
+    a row that is on is 0.  ``work`` as for ``rank_attribution``: sized by
+    ``rank_attribution_plan(R, K, top)``, allocated when the plan needs one and none is given.
+    ``histograms.score_rank_attribution`` is the host twin."""
+    top, kind_code = attribution_request(top, kind)
+    for name, t in (("num", num), ("med", med), ("avg", avg)):
+        N.require_device(t, name)
+    if med.dim() != 2 or num.shape != med.shape or avg.shape != med.shape:
+        raise ValueError("num, med and avg must share one shape [R, K]")
+    R, K = med.shape
+    if num.dtype != torch.int32 or med.dtype not in (torch.float32, torch.float64):
+        raise TypeError("num must be int32, med and avg float32 or float64")
+    if avg.dtype != med.dtype or (hist is not None and hist.dtype != med.dtype):
+        raise TypeError("med, avg and hist must share one float dtype")
+    if not (num.is_contiguous() and med.is_contiguous() and avg.is_contiguous()):
+        raise ValueError("num, med and avg must be contiguous")
+    if kind_code == N.NVRX_ATTR_RELATIVE and ref is None:
+        raise ValueError("kind='relative' needs ref")
+    if kind_code == N.NVRX_ATTR_INDIVIDUAL and hist is None:
+        raise ValueError("kind='individual' needs hist")
+    if hist_index is not None and hist_stride <= 0:
+        raise ValueError("hist_index needs hist_stride")
+    if R >= 1 << 31 or K >= 1 << 31:
+        raise ValueError("R and K must be below 2^31")
+    d = med.device
+    _u8_vector(rows, "rows", R)
+    if out is not None:
+        _tail_tensor(out.idx, "out.idx", torch.int32, (K, top))
+        _tail_tensor(out.loss, "out.loss", torch.float64, (K, top))
+        _tail_tensor(out.score, "out.score", torch.float64, (K, top))
+        _tail_tensor(out.taken, "out.taken", torch.int32, (K,))
+        _tail_tensor(out.positive, "out.positive", torch.int32, (K,))
+    need = rank_attribution_plan(R, K, top)[2]
+    if work is not None:
+        N.require_device(work, "work")
+        if (work.dtype != torch.uint8 or not work.is_contiguous() or work.numel() < need or
+                work.data_ptr() % 8):
+            raise ValueError(f"work must be a contiguous, 8-byte aligned uint8 tensor of at least "
+                             f"{need} bytes (rank_attribution_plan)")
+    # every refusal is above: nothing has been allocated yet
+    if out is None:
+        out = ScoreRankAttribution.empty(K, top, d)
+    if work is None and need:
+        work = torch.empty(need, dtype=torch.uint8, device=d)
+    a = N.ScoreRankArgs(R, K, int(med.dtype == torch.float64), num.data_ptr(), med.data_ptr(),
+                        avg.data_ptr(), N.ptr(col_valid), N.ptr(ref), N.ptr(ref_index),
+                        N.ptr(ref_missing), N.ptr(hist), N.ptr(hist_index), hist_stride,
+                        kind_code, top, N.ptr(rows), out.idx.data_ptr(), out.loss.data_ptr(),
+                        out.score.data_ptr(), out.taken.data_ptr(), out.positive.data_ptr(),
+                        N.ptr(err), N.ptr(work))
+    N.call("nvrx_score_rank_attribution", ctypes.byref(a), _stream(stream))
+    return out
+
+
 def finalize_scores(partials: torch.Tensor, R: int, nshards: int = 1, round_f32: bool = False,
                     thr_rel: float = 0.75, thr_ind: float = 0.75, rel=True, ind=True, err=None,
                     out: Optional[dict] = None, stream=None):
